@@ -15,12 +15,19 @@ Multi-GPU: objects are independent, so ranks hold disjoint batche
 has no collective ("weak" scaling: 256 objects per GPU).  Timing: barrier + synchronize, K steps,
 synchronize + barrier, MAX over ranks.
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps and prints the line (metric, value, ms_per_step, ...).
+With --full the JSON line also carries
   roofline     - the dominant kernel (k_trunk4: feature transform + conv2..conv4 + max-pool, 57 % of the
                  FLOPs) measured live with HIP events recorded on its launch stream inside the timed
                  region, against the dense fp32 MFMA peak (157.3 TFLOP/s);
-  cpu_baseline - the oracle (torch CPU port of the reference path) timed on this box's host cores on a
+  maxpool_standalone, split_mode, single_image, train_fp32 - measurements outside the timed region;
+  cpu_baseline - the oracle (torch CPU port of the reference path) timed on the host cores on a
                  bounded sample (rank 0, N=1 only).
+
+--dump-outputs DIR writes what the timed path returned in its last step as DIR/<name>.npy (float32):
+refine - pose_0..pose_K / scale_0..scale_K; train - the last iteration's pose / scale, its loss terms
+(loss.<key>) and the parameters after the last optimizer step (param.<name>, rank 0).  Ranks other than
+0 add .rank<r> to the name.  Inputs and weights are seeded: the same arguments give the same inputs.
 """
 import argparse
 import json
@@ -132,6 +139,23 @@ def comm_info(dist, dev, world, rank, local_rank):
     return info
 
 
+DUMP_LIMIT_BYTES = 64 * 2**20
+
+
+def dump_outputs(path, arrays, rank):
+    """--dump-outputs: `arrays` (name -> tensor, what a caller of the timed path received from its last step) as
+    `path/<name>.npy` in float32; ranks other than 0 add `.rank<r>`."""
+    import numpy as np
+
+    host = {k: v.detach().float().cpu().numpy() for k, v in arrays.items()}
+    total = sum(a.nbytes for a in host.values())
+    assert total <= DUMP_LIMIT_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES} byte cap"
+    os.makedirs(path, exist_ok=True)
+    suffix = "" if rank == 0 else f".rank{rank}"
+    for k, a in host.items():
+        np.save(os.path.join(path, f"{k}{suffix}.npy"), a)
+
+
 def bench_dryrun(args, world, rank):
     import torch.distributed as dist
 
@@ -145,7 +169,7 @@ def bench_dryrun(args, world, rank):
         if dist is not None:
             dist.barrier()
 
-    x = torch.randn(64, 64)
+    x = torch.randn(64, 64, generator=torch.Generator().manual_seed(rank))
     for _ in range(args.warmup):
         x = torch.tanh(x @ x)
     barrier()
@@ -157,6 +181,8 @@ def bench_dryrun(args, world, rank):
             dist.all_reduce(g)  # stands in for DDP's gradient all-reduce
     barrier()
     dt, per_rank, seen = rank_stats(dist, dev, time.perf_counter() - t0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"x": x}, rank)
     if rank == 0:
         emit(({
             "metric": "DRYRUN (launcher / rendezvous plumbing only, no GPU work)", "value": None, "unit": "object-iterations/s",
@@ -381,13 +407,14 @@ def init_world1_group(dev):
     return tdist
 
 
-def run_train(cfg_fn, dev, dist, rank, dtype, steps, warmup, ddp_kwargs=None, probe=None, freeze_dead=False):
+def run_train(cfg_fn, dev, dist, rank, dtype, steps, warmup, ddp_kwargs=None, probe=None, freeze_dead=False, keep=None):
     """BASELINE.json configs 3/4: one step = the reference's train loop body for one data batch
     (core/catre/engine/engine.py:293-355): K_ITER x (pose-apply, forward + loss, backward, optimizer step), the fed-back
     pose detached.  With N > 1 the model is wrapped in DistributedDataParallel exactly like
     core/catre/main_catre.py:154-160 and gradients are all-reduced over RCCL (17.19 MB per backward).  `ddp_kwargs` (a dict,
     possibly empty) forces the same wrap on a single rank (`--ddp-world1`: the reducer's cost without the wire); `probe` (a
-    dict) receives the gradient order of one extra, untimed backward against the wrapper's bucket plan.
+    dict) receives the gradient order of one extra, untimed backward against the wrapper's bucket plan; `keep` (a dict)
+    receives what the last timed step returned: its last iteration's outputs and loss terms, and the model's parameters.
     -> seconds for `steps` steps on this rank (barrier + synchronize on both sides)."""
     from catre_amd import synth
     from catre_amd.batching import batch_updater_test
@@ -433,6 +460,8 @@ def run_train(cfg_fn, dev, dist, rank, dtype, steps, warmup, ddp_kwargs=None, pr
                               obj_kps=b["obj_kps"], mean_scales=b["obj_mean_scales"], sym_info=sym_info, do_loss=True,
                               cur_iter=it)
             poses_est, scales_est = out[f"pose_{it}"].detach(), out[f"scale_{it}"].detach()
+            if keep is not None and it == K_ITER:
+                keep["out"], keep["loss"] = out, ld
             if gprobe[0] is not None and it == K_ITER:
                 gprobe[0].begin()
             sum(ld.values()).backward()
@@ -457,6 +486,8 @@ def run_train(cfg_fn, dev, dist, rank, dtype, steps, warmup, ddp_kwargs=None, pr
     barrier()
     dt = time.perf_counter() - t0
     assert torch.isfinite(last).all()
+    if keep is not None:
+        keep["params"] = dict(model.named_parameters())
     if probe is not None:  # one more step, untimed, with a hook behind every gradient accumulation
         gprobe[0] = GradOrderProbe(list(model.named_parameters()))
         one_step()
@@ -527,7 +558,14 @@ def bench_train(args, world, rank, dev, dist, cfg_fn):
         init_world1_group(dev)
         ddp1 = {"bucket_cap_mb": args.bucket_cap_mb, "gradient_as_bucket_view": bool(args.bucket_view)}
     probe = {} if ddp1 is not None else None
-    dt = run_train(cfg_fn, dev, dist, rank, args.dtype, args.steps, args.warmup, ddp_kwargs=ddp1, probe=probe)
+    keep = {} if args.dump_outputs else None
+    dt = run_train(cfg_fn, dev, dist, rank, args.dtype, args.steps, args.warmup, ddp_kwargs=ddp1, probe=probe, keep=keep)
+    if keep is not None:
+        arrays = dict(keep["out"])
+        arrays.update({f"loss.{k}": v for k, v in keep["loss"].items()})
+        if rank == 0:  # the ranks of a DDP job hold the same parameters
+            arrays.update({f"param.{k}": v for k, v in keep["params"].items()})
+        dump_outputs(args.dump_outputs, arrays, rank)
     dt, per_rank_ms, ranks_seen = rank_stats(dist, dev, dt)
     comm = comm_info(dist, dev, world, rank, dev.index)
     if rank == 0:
@@ -564,9 +602,14 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: roofline, stand-alone max-pool, split / single-image / training extras and the "
+                         "cpu_baseline (each --no-* flag below drops one of them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-train-extra", action="store_true", help="skip the bounded fp32 training measurement of the default line")
-    ap.add_argument("--no-small-extra", action="store_true", help="skip the single-image (B=1 / B=4) measurement of the default line")
+    ap.add_argument("--no-train-extra", action="store_true", help="skip the bounded fp32 training measurement of the --full line")
+    ap.add_argument("--no-small-extra", action="store_true", help="skip the single-image (B=1 / B=4) measurement of the --full line")
     ap.add_argument("--mode", choices=("refine", "train"), default="refine",
                     help="refine: the headline inference metric (default); train: configs 3/4 (fwd+loss+bwd+step)")
     ap.add_argument("--dtype", choices=("fp32", "split", "bf16"), default="fp32",
@@ -575,13 +618,14 @@ def main():
     ap.add_argument("--shape", choices=("headline", "config5", "config2"), default="headline",
                     help="headline: B=256, N=M=1024, K=4; config5: N=2048 observed, M=1024, K=8; config2: B=64 (BASELINE "
                          "configs[1] as written - the headline metric is quoted at B=256)")
-    ap.add_argument("--no-split-extra", action="store_true", help="skip the split-mode measurement of the default line")
-    ap.add_argument("--no-ddp-extra", action="store_true", help="skip the DDP-world-1 measurement of the default line")
+    ap.add_argument("--no-split-extra", action="store_true", help="skip the split-mode measurement of the --full line")
+    ap.add_argument("--no-ddp-extra", action="store_true", help="skip the DDP-world-1 measurement of the --full line")
     ap.add_argument("--ddp-world1", action="store_true",
                     help="--mode train on ONE GPU inside the reference's DistributedDataParallel wrap (one-rank RCCL group)")
     ap.add_argument("--bucket-cap-mb", type=float, default=25, help="--ddp-world1: DDP bucket_cap_mb (torch default 25)")
     ap.add_argument("--bucket-view", action="store_true", help="--ddp-world1: gradient_as_bucket_view=True")
     args = ap.parse_args()
+    full = args.full
     global N_PTS, K_ITER, B_PER_GPU
     if args.shape == "config5":
         N_PTS, K_ITER = 2048, 8
@@ -649,21 +693,25 @@ def main():
     for _ in range(args.warmup):
         model.refine(batch, n_iter=K_ITER)
     nrec = args.steps * K_ITER
-    hip.profile_kernel("trunk", nrec)
+    if full:
+        hip.profile_kernel("trunk", nrec)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         out = model.refine(batch, n_iter=K_ITER)
     barrier()
     dt = time.perf_counter() - t0
-    trunk_ms = hip.profile_collect(nrec)
-    hip.profile_kernel(None, 0)
+    if full:
+        trunk_ms = hip.profile_collect(nrec)
+        hip.profile_kernel(None, 0)
     assert torch.isfinite(out[f"pose_{K_ITER}"]).all()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, out, rank)
 
     # stand-alone channel-wise max-pool [B,1024,N] -> [B,1024] (the HBM-bound figure the north star asks
     # for; in the fused path these bytes never exist).  Outside the timed region, rank 0 only.
     maxpool = None
-    if rank == 0:
+    if full and rank == 0:
         from catre_amd.runtime import colmax
 
         xs = torch.randn(B_PER_GPU, 1024, N_PTS, device=dev)
@@ -686,7 +734,7 @@ def main():
     # the same batch through the split compute mode (outside the timed region, rank 0 only): throughput and its
     # deviation from the fp32 kernels' result - reported next to the headline, never as `value`
     split_extra = None
-    if rank == 0 and args.dtype == "fp32" and not args.no_split_extra:
+    if full and rank == 0 and args.dtype == "fp32" and not args.no_split_extra:
         model.cfg.MODEL.CATRE.COMPUTE_DTYPE = "split"
         for _ in range(2):
             osp = model.refine(batch, n_iter=K_ITER)
@@ -710,7 +758,7 @@ def main():
     # image = a handful of objects per call (catre_evaluator.py:292-311).  Object 0 of the batch alone, K refine
     # iterations, and the check that it gets the very bits it got inside the batch of 256 (latency path).
     small_extra = None
-    if rank == 0 and world == 1 and args.dtype == "fp32" and args.shape == "headline" and not args.no_small_extra:
+    if full and rank == 0 and world == 1 and args.dtype == "fp32" and args.shape == "headline" and not args.no_small_extra:
         small_extra = {"what": "K=4 refine of 1 / 4 objects (the reference evaluator's shape: one image per call), fp32 "
                                "kernels, whole K loop as one C call; outside the timed region", "unit": "ms per K=4 refine"}
         for nb in (1, 4):
@@ -730,7 +778,7 @@ def main():
     # BASELINE.json config 3 next to the headline (outside the timed region, rank 0 of a 1-GPU run only): the training
     # step of engine.py:293-355 at the same batch, fp32, a few steps - so the driver's record carries a train number too
     train_extra = None
-    if rank == 0 and world == 1 and args.dtype == "fp32" and args.shape == "headline" and not args.no_train_extra:
+    if full and rank == 0 and world == 1 and args.dtype == "fp32" and args.shape == "headline" and not args.no_train_extra:
         tsteps = 3
         tdt = run_train(cfg_fn, dev, None, 0, "fp32", tsteps, 1)
         train_extra = {"what": "BASELINE config 3: K=4 x (pose-apply, forward + device-side loss, backward, fused Ranger step) of "
@@ -764,23 +812,24 @@ def main():
     if rank == 0:
         obj_iters = world * B_PER_GPU * K_ITER * args.steps
         value = obj_iters / dt
-        trunk_avg_ms = sum(trunk_ms) / max(len(trunk_ms), 1)
-        trunk_flops = B_PER_GPU * (N_PTS + M_PTS) * TRUNK_FLOPS_PER_POINT  # all points of both clouds per launch
-        achieved = trunk_flops / (trunk_avg_ms * 1e-3) / 1e12 if trunk_ms else None
-        # HBM bytes of the dominant kernel cannot be counted inside this run (PMC passes serialise the kernels and need
-        # rocprofv3): the figure is the one collected from this build by profiles/pmc.sh (separate --pmc passes, gfx950
-        # FETCH_SIZE x2 correction) and committed next to its summary; `traffic_source` says so in the line itself
-        traffic, traffic_source = None, None
-        import glob
-        pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_trunk_hbm_bytes.json")))  # newest round's pass
-        if pmcs and args.dtype == "fp32" and args.shape == "headline":
-            pmc = pmcs[-1]
-            tag = os.path.basename(pmc)[:3]
-            with open(pmc) as f:
-                traffic = json.load(f).get("hbm_bytes_per_launch")
-            traffic_source = (f"profiles/{os.path.basename(pmc)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
-                              f"build (profiles/pmc.sh, profiles/{tag}_pmc_summary.csv), not measured in this run; algorithmic "
-                              f"bytes per launch = {B_PER_GPU * (N_PTS + M_PTS) * 12}")
+        if full:
+            trunk_avg_ms = sum(trunk_ms) / max(len(trunk_ms), 1)
+            trunk_flops = B_PER_GPU * (N_PTS + M_PTS) * TRUNK_FLOPS_PER_POINT  # all points of both clouds per launch
+            achieved = trunk_flops / (trunk_avg_ms * 1e-3) / 1e12 if trunk_ms else None
+            # HBM bytes of the dominant kernel cannot be counted inside this run (PMC passes serialise the kernels and need
+            # rocprofv3): the figure is the one collected from this build by profiles/pmc.sh (separate --pmc passes, gfx950
+            # FETCH_SIZE x2 correction) and committed next to its summary; `traffic_source` says so in the line itself
+            traffic, traffic_source = None, None
+            import glob
+            pmcs = sorted(glob.glob(os.path.join(ROOT, "profiles", "r[0-9][0-9]_trunk_hbm_bytes.json")))  # newest round's pass
+            if pmcs and args.dtype == "fp32" and args.shape == "headline":
+                pmc = pmcs[-1]
+                tag = os.path.basename(pmc)[:3]
+                with open(pmc) as f:
+                    traffic = json.load(f).get("hbm_bytes_per_launch")
+                traffic_source = (f"profiles/{os.path.basename(pmc)}: rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this "
+                                  f"build (profiles/pmc.sh, profiles/{tag}_pmc_summary.csv), not measured in this run; algorithmic "
+                                  f"bytes per launch = {B_PER_GPU * (N_PTS + M_PTS) * 12}")
         path_flops = flops_per_object_iteration(N_PTS, M_PTS)
         line = {
             "metric": f"pose-refine iters/sec (B={B_PER_GPU}, N={N_PTS}, K={K_ITER})"
@@ -811,7 +860,9 @@ def main():
             },
             "path_tflops": round(value * path_flops / 1e12, 2),
             "path_frac_of_mfma_peak": round(value * path_flops / 1e12 / (mfma_peak * world), 4),
-            "roofline": {
+        }
+        if full:
+            line["roofline"] = {
                 "kernel": "k_trunk_bf2" if bf16 else ("k_trunk_split" if split else "k_trunk4"),  # (full grids: the forms that fill the chip)
                 "bound": "mfma",
                 "achieved": round(achieved, 2) if achieved else None,
@@ -823,16 +874,15 @@ def main():
                 "avg_launch_ms": round(trunk_avg_ms, 4),
                 "launches_timed": len(trunk_ms),
                 "flops_per_launch": trunk_flops,
-            },
-        }
-        line["maxpool_standalone"] = maxpool
+            }
+            line["maxpool_standalone"] = maxpool
         if split_extra is not None:
             line["split_mode"] = split_extra
         if small_extra is not None:
             line["single_image"] = small_extra
         if train_extra is not None:
             line["train_fp32"] = train_extra
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg_fn, sd)
         emit(line)
     if dist is not None:

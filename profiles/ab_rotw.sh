@@ -2,7 +2,7 @@
 # A/B of the one-wave-per-SIMD rotation-head kernel (k_rot_l1w, CATRE_ROTW=1, default) against k_rot_l1<1> on one box:
 #   profiles/ab_rotw.sh -> gpurun_out/r06_ab_rotw.jsonl (bench lines), gpurun_out/r06_ab_rotw_kernels.txt (rocprof averages)
 o=gpurun_out
-F="--no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra"
+F="--full --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra"
 line() { python -c "
 import sys, json
 r = json.loads(sys.stdin.read()); print(json.dumps({'variant': '$1', 'value': r['value'], 'ms_per_step': r['ms_per_step'], 'trunk_ms': r['roofline']['avg_launch_ms'], 'frac': r['roofline']['frac']}))"; }

@@ -2,7 +2,7 @@
 # A/B of the one-wave-per-SIMD trunk (k_trunk4, CATRE_TRUNK4=1, default) against the 8-wave k_trunk on one box:
 #   profiles/ab_trunk4.sh [extra lib ...] -> gpurun_out/r05_ab_trunk4.jsonl, gpurun_out/r05_trunk4_phases.txt
 o=gpurun_out
-F="--no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra"
+F="--full --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra"
 line() { python -c "
 import sys, json
 r = json.loads(sys.stdin.read()); print(json.dumps({'variant': '$1', 'value': r['value'], 'ms_per_step': r['ms_per_step'], 'trunk_ms': r['roofline']['avg_launch_ms'], 'frac': r['roofline']['frac']}))"; }

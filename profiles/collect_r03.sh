@@ -10,10 +10,10 @@ if want tests; then
   cat $o/r03_gputest.log
 fi
 if want bench; then
-  python bench.py > $o/r03_bench_n1.json 2> $o/r03_bench_n1.err
-  { python bench.py --dtype split --no-cpu-baseline; python bench.py --dtype bf16 --no-cpu-baseline;
-    python bench.py --shape config5 --no-cpu-baseline --steps 5; python bench.py --shape config5 --dtype bf16 --no-cpu-baseline --steps 5;
-    python bench.py --shape config5 --dtype split --no-cpu-baseline --steps 5; } 2>/dev/null | grep '^{' > $o/r03_modes_bench.jsonl
+  python bench.py --full > $o/r03_bench_n1.json 2> $o/r03_bench_n1.err
+  { python bench.py --full --dtype split --no-cpu-baseline; python bench.py --full --dtype bf16 --no-cpu-baseline;
+    python bench.py --full --shape config5 --no-cpu-baseline --steps 5; python bench.py --full --shape config5 --dtype bf16 --no-cpu-baseline --steps 5;
+    python bench.py --full --shape config5 --dtype split --no-cpu-baseline --steps 5; } 2>/dev/null | grep '^{' > $o/r03_modes_bench.jsonl
   { python bench.py --mode train --steps 4 --warmup 4; python bench.py --mode train --dtype bf16 --steps 4 --warmup 4;
     python bench.py --mode train --dtype split --steps 4 --warmup 4; } 2>/dev/null | grep '^{' > $o/r03_train_bench.jsonl
 fi
@@ -25,7 +25,7 @@ if want small; then
   profiles/prof.sh $o/r03_b1_kernel_stats.csv python $PWD/profiles/b1_profile.py 1 50
 fi
 if want prof; then
-  profiles/prof.sh $o/r03_kernel_stats.csv python $PWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-train-extra --no-small-extra
+  profiles/prof.sh $o/r03_kernel_stats.csv python $PWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-train-extra --no-small-extra
 fi
 if want train; then
   python profiles/train_step.py 16 64 256 2>/dev/null | grep '^{' > $o/r03_train_step.jsonl
@@ -38,8 +38,8 @@ if want pmctrain; then   # counters for config 3 (MFMA busy, FETCH 
   rm -rf /tmp/pmc_r03t
 fi
 if want bf16; then
-  profiles/prof.sh $o/r03_bf16_kernel_stats.csv python $PWD/bench.py --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline
-  profiles/prof.sh $o/r03_split_kernel_stats.csv python $PWD/bench.py --dtype split --steps 5 --warmup 2 --no-cpu-baseline
+  profiles/prof.sh $o/r03_bf16_kernel_stats.csv python $PWD/bench.py --full --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline
+  profiles/prof.sh $o/r03_split_kernel_stats.csv python $PWD/bench.py --full --dtype split --steps 5 --warmup 2 --no-cpu-baseline
   profiles/pmc.sh /tmp/pmc_r03b --dtype bf16 > /dev/null 2>&1
   python profiles/summarize_pmc.py /tmp/pmc_r03b $o/r03_bf16_pmc_summary.csv r03bf16 > /dev/null
   rm -rf /tmp/pmc_r03b

@@ -10,10 +10,10 @@ if want tests; then
   cat $o/r05_gputest.log
 fi
 if want bench; then
-  python bench.py > $o/r05_bench_n1.json 2> $o/r05_bench_n1.err
-  { python bench.py --dtype split --no-cpu-baseline; python bench.py --dtype bf16 --no-cpu-baseline;
-    python bench.py --shape config5 --no-cpu-baseline --steps 5; python bench.py --shape config5 --dtype bf16 --no-cpu-baseline --steps 5;
-    python bench.py --shape config5 --dtype split --no-cpu-baseline --steps 5; } 2>/dev/null | grep '^{' > $o/r05_modes_bench.jsonl
+  python bench.py --full > $o/r05_bench_n1.json 2> $o/r05_bench_n1.err
+  { python bench.py --full --dtype split --no-cpu-baseline; python bench.py --full --dtype bf16 --no-cpu-baseline;
+    python bench.py --full --shape config5 --no-cpu-baseline --steps 5; python bench.py --full --shape config5 --dtype bf16 --no-cpu-baseline --steps 5;
+    python bench.py --full --shape config5 --dtype split --no-cpu-baseline --steps 5; } 2>/dev/null | grep '^{' > $o/r05_modes_bench.jsonl
   { python bench.py --mode train --steps 4 --warmup 4; python bench.py --mode train --dtype bf16 --steps 4 --warmup 4;
     python bench.py --mode train --dtype split --steps 4 --warmup 4; } 2>/dev/null | grep '^{' > $o/r05_train_bench.jsonl
 fi
@@ -25,7 +25,7 @@ if want small; then
   profiles/prof.sh $o/r05_b1_kernel_stats.csv python $PWD/profiles/b1_profile.py 1 50
 fi
 if want prof; then
-  profiles/prof.sh $o/r05_kernel_stats.csv python $PWD/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra
+  profiles/prof.sh $o/r05_kernel_stats.csv python $PWD/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra
 fi
 if want train; then
   python profiles/train_step.py 16 64 256 2>/dev/null | grep '^{' > $o/r05_train_step.jsonl
@@ -40,8 +40,8 @@ if want pmctrain; then   # counters for config 3 (MFMA busy, FETCH 
   rm -rf /tmp/pmc_r05t
 fi
 if want bf16; then
-  profiles/prof.sh $o/r05_bf16_kernel_stats.csv python $PWD/bench.py --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline
-  profiles/prof.sh $o/r05_split_kernel_stats.csv python $PWD/bench.py --dtype split --steps 5 --warmup 2 --no-cpu-baseline
+  profiles/prof.sh $o/r05_bf16_kernel_stats.csv python $PWD/bench.py --full --dtype bf16 --steps 5 --warmup 2 --no-cpu-baseline
+  profiles/prof.sh $o/r05_split_kernel_stats.csv python $PWD/bench.py --full --dtype split --steps 5 --warmup 2 --no-cpu-baseline
   profiles/pmc.sh /tmp/pmc_r05b --dtype bf16 > /dev/null 2>&1
   python profiles/summarize_pmc.py /tmp/pmc_r05b $o/r05_bf16_pmc_summary.csv r05bf16 > /dev/null
   rm -rf /tmp/pmc_r05b
@@ -60,5 +60,5 @@ if want pmc; then
 fi
 if want sweep; then
   python profiles/parity_sweep.py 2>/dev/null | grep '^{' > $o/r05_parity_sweep.jsonl
-  python bench.py --shape config2 --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra 2>/dev/null | grep '^{' > $o/r05_config2_bench.json
+  python bench.py --full --shape config2 --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra 2>/dev/null | grep '^{' > $o/r05_config2_bench.json
 fi

@@ -8,7 +8,7 @@ mkdir -p "$out"
 cd /tmp && export TMPDIR=/tmp
 run() {  # name, counters...
   local name=$1; shift
-  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out/$name" -- python "$root/bench.py" --steps 2 --warmup 1 \
+  rocprofv3 --pmc "$@" --kernel-trace --output-format csv -d "$out/$name" -- python "$root/bench.py" --full --steps 2 --warmup 1 \
     --no-cpu-baseline --no-train-extra --no-small-extra --no-split-extra "${BENCH_ARGS[@]}" > "$out/$name.log" 2>&1 || tail -3 "$out/$name.log"
 }
 BENCH_ARGS=("$@")

@@ -42,6 +42,21 @@ def test_single_rank_does_not_spawn():
     assert line["n_gpus"] == 1 and line["ranks_seen"] == 1
 
 
+def test_dump_outputs_writes_one_seeded_file_per_rank(tmp_path):
+    """`--dump-outputs DIR` through the launcher: rank 0 writes `<name>.npy`, rank r `<name>.rank<r>.npy`, float32; the same
+    arguments give the same arrays."""
+    import numpy as np
+
+    for run in ("a", "b"):
+        r, lines = _run(["--gpus", "2", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / run)])
+        assert r.returncode == 0, r.stderr[-2000:]
+        assert len(lines) == 1
+    x0, x1 = np.load(tmp_path / "a" / "x.npy"), np.load(tmp_path / "a" / "x.rank1.npy")
+    assert x0.dtype == np.float32 and x0.shape == (64, 64) and np.isfinite(x0).all()
+    assert not np.array_equal(x0, x1)   # ranks hold different inputs
+    assert np.array_equal(x0, np.load(tmp_path / "b" / "x.npy")) and np.array_equal(x1, np.load(tmp_path / "b" / "x.rank1.npy"))
+
+
 def test_world_size_mismatch_is_an_error():
     r, _ = _run(["--gpus", "2"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0 and "does not match" in r.stderr

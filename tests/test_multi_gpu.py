@@ -96,7 +96,7 @@ def test_bench_launcher_with_two_rank_processes_sharing_one_gpu():
     REAL refine / training work on the device.  The line is marked `shared_gpu` - it is plumbing evidence, never a scaling
     number."""
     env = {"CATRE_BENCH_SHARE_GPU": "1"}
-    line = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", env=env)
+    line = _bench("--gpus", "2", "--steps", "2", "--warmup", "1", "--full", env=env)
     assert line["n_gpus"] == 2 and line["ranks_seen"] == 2 and len(line["per_rank_ms"]) == 2 and line["shared_gpu"] is True
     assert line["comm"]["backend"] == "gloo" and {r["rank"] for r in line["comm"]["ranks"]} == {0, 1}
     assert line["value"] > 0 and line["roofline"]["frac"] > 0
