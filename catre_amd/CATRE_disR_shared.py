@@ -24,6 +24,8 @@ from .runtime import HipRuntime, opts_from_cfg
 
 logger = logging.getLogger(__name__)
 
+_FP16_NAMES = ("fp16", "float16")  # cfg.MODEL.CATRE.COMPUTE_DTYPE of the fp16-operand inference mode
+
 
 class CATRE_disR_shared(nn.Module):
     def __init__(self, cfg, pcl_net, rot_head, ts_head):
@@ -55,13 +57,16 @@ class CATRE_disR_shared(nn.Module):
         self._opts_bf16.compute_dtype = hip.DTYPE_BF16
         self._opts_split = type(self._opts).from_buffer_copy(self._opts)
         self._opts_split.compute_dtype = hip.DTYPE_SPLIT
+        self._opts_f16 = type(self._opts).from_buffer_copy(self._opts)
+        self._opts_f16.compute_dtype = hip.DTYPE_F16
 
     def _inference_opts(self):
         """fp32 kernels unless reduced precision is requested the way the reference requests it - by running
         the forward under ``torch.cuda.amp.autocast`` (``engine.py:304``, ``TEST.AMP_TEST`` in
         ``catre_evaluator.py``) - or explicitly with ``cfg.MODEL.CATRE.COMPUTE_DTYPE = "bf16"``.  Reduced precision
         means bf16 GEMM operands with fp32 accumulation / GroupNorm statistics / SO(3) update (an fp16 autocast
-        request maps to the same kernels)."""
+        request maps to the same kernels).  ``COMPUTE_DTYPE = "fp16"`` selects the same structure with fp16 operands -
+        the dtype the reference's autocast uses on "cuda" - for inference only."""
         want = self.cfg.MODEL.CATRE.get("COMPUTE_DTYPE", None)
         if want is None:
             from .train_ops import autocast_on
@@ -73,7 +78,9 @@ class CATRE_disR_shared(nn.Module):
             return self._opts
         if want == "split":
             return self._opts_split
-        raise ValueError(f"MODEL.CATRE.COMPUTE_DTYPE={want!r}: expected 'fp32', 'split' or 'bf16'")
+        if want in _FP16_NAMES:
+            return self._opts_f16
+        raise ValueError(f"MODEL.CATRE.COMPUTE_DTYPE={want!r}: expected 'fp32', 'split', 'bf16' or 'fp16'")
 
     # -- runtime is per-instance state that must never be shared by copies of the module
     def __getstate__(self):
@@ -140,6 +147,9 @@ class CATRE_disR_shared(nn.Module):
         # training / autograd: layer-by-layer HIP ops chained by torch.autograd (catre_amd/train_forward.py).
         # Like the reference, gradients flow to the parameters only: the caller detaches the fed-back pose
         # (engine.py:324-325) and x / tfd_kps come from the data batch.
+        if self.cfg.MODEL.CATRE.get("COMPUTE_DTYPE", None) in _FP16_NAMES:
+            raise NotImplementedError("MODEL.CATRE.COMPUTE_DTYPE='fp16' is an inference mode (no_grad, do_loss=False, "
+                                      "refine); the training forward runs in 'bf16', 'split' or 'fp32'")
         from .train_forward import forward_train
         from .train_ops import amp_mode, train_kernels
 

@@ -52,6 +52,49 @@ __device__ __forceinline__ u32x4 pack_bf8(const float (&v)[8]) {
   return w;
 }
 
+// Operand type of the reduced-precision INFERENCE kernels (template argument OT): its three type-specific pieces - the
+// MFMA, narrowing (RNE) and widening of a packed pair.  OpBf16 is the bf16 path above (widening by bits); OpF16 takes
+// fp16 operands (COMPUTE_DTYPE="fp16", the dtype of the reference's autocast on "cuda"): the same layouts, the same
+// rounding points, v_mfma_f32_32x32x16_f16 at the bf16 form's rate, v_cvt_pk_f16_f32 to narrow (RNE - the pkrtz form
+// rounds toward zero) and v_cvt_f32_f16 to widen.  The training (SAVE) forms and the backward kernels stay bf16-only.
+typedef _Float16 f16x8_t __attribute__((ext_vector_type(8)));
+typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
+struct OpBf16 {
+  typedef __bf16 T;
+  static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) { return mfma_bf(a, b, c); }
+  static __device__ __forceinline__ unsigned pack2(float lo, float hi) { return pack_bf2(lo, hi); }
+  static __device__ __forceinline__ float lo(unsigned u) { return bf_lo(u); }
+  static __device__ __forceinline__ float hi(unsigned u) { return bf_hi(u); }
+};
+struct OpF16 {
+  typedef _Float16 T;
+  static __device__ __forceinline__ f32x16 mfma(u32x4 a, u32x4 b, f32x16 c) {
+    return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8_t, a), __builtin_bit_cast(f16x8_t, b), c, 0, 0,
+                                                  0);
+  }
+  static __device__ __forceinline__ unsigned pack2(float lo, float hi) {  // v_cvt_pk_f16_f32 (RNE)
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    f2 v = {lo, hi};
+    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, f16x2_t));
+  }
+  static __device__ __forceinline__ float lo(unsigned u) { return (float)__builtin_bit_cast(f16x2_t, u)[0]; }
+  static __device__ __forceinline__ float hi(unsigned u) { return (float)__builtin_bit_cast(f16x2_t, u)[1]; }
+};
+template <class OT>
+constexpr bool is_f16_op() {
+  return __is_same(OT, OpF16);
+}
+
+template <class OT>
+__device__ __forceinline__ u32x4 pack8(const float (&v)[8]) {
+  u32x4 w;
+  w[0] = OT::pack2(v[0], v[1]);
+  w[1] = OT::pack2(v[2], v[3]);
+  w[2] = OT::pack2(v[4], v[5]);
+  w[3] = OT::pack2(v[6], v[7]);
+  return w;
+}
+
 // rows of 256 channels stored as fp32 (HB = false) or bf16 (HB = true): four consecutive channels of row-quad index i4
 // (= row * 64 + channel / 4).  The reduced-precision training heads keep their [rows,256] activations in bf16 - what
 // torch.autocast's Conv1d outputs are (engine.py:304) - and every pass over them moves half the bytes.
@@ -129,7 +172,7 @@ __global__ void k_pack_frag_bf(const float* __restrict__ src, int ld, int coloff
 // per-lane base with a compile-time constant - (chunk ^ key) << 4 == (chunk << 4) ^ (key << 4), and neither overlaps the
 // row bits - instead of eight (sixteen past 64 KiB) per-lane pointers held across the sweep.
 typedef __attribute__((address_space(3))) const u32x4 lds_cu32x4;
-template <int MB, int NB, bool SWAP, int CP, int PFD, int PFB = 1, bool XA = false>
+template <int MB, int NB, bool SWAP, int CP, int PFD, int PFB = 1, bool XA = false, class OT = OpBf16>
 struct GemmPipeB {
   static constexpr int NKC = CP / 2;
   static_assert(PFD >= 1 && PFD <= NKC && PFB >= 1 && PFB <= PFD, "prefetch depth");
@@ -209,7 +252,7 @@ struct GemmPipeB {
       for (int mb = 0; mb < MB; ++mb)
 #pragma unroll
         for (int nb = 0; nb < NB; ++nb)
-          acc[mb][nb] = SWAP ? mfma_bf(b[cb][nb], a[ca][mb], acc[mb][nb]) : mfma_bf(a[ca][mb], b[cb][nb], acc[mb][nb]);
+          acc[mb][nb] = SWAP ? OT::mfma(b[cb][nb], a[ca][mb], acc[mb][nb]) : OT::mfma(a[ca][mb], b[cb][nb], acc[mb][nb]);
       __builtin_amdgcn_sched_barrier(0);
     }
   }
@@ -217,7 +260,7 @@ struct GemmPipeB {
 
 // "normal"-orientation epilogue: act(acc + bias) -> bf16 image, one 16-byte chunk per 8 results.
 // mblk0 = absolute index of the wave tile's first 32-channel block; img = image row of point 0 of the tile.
-template <int MB, int NB, bool RELU, int CP>
+template <int MB, int NB, bool RELU, int CP, class OT = OpBf16>
 __device__ __forceinline__ void store_tile_bf(const f32x16 (&acc)[MB][NB], u32x4* img, int mblk0,
                                               const f32x4 (&bv)[MB][4], int lane) {
   const int n = lane & 31, h = lane >> 5, key = bf_key<CP>(n);
@@ -236,12 +279,13 @@ __device__ __forceinline__ void store_tile_bf(const f32x16 (&acc)[MB][NB], u32x4
             const float t = acc[mb][nb][4 * (2 * s + g2) + q] + bv[mb][2 * s + g2][q];
             v[4 * g2 + q] = RELU ? fmaxf(t, 0.f) : t;
           }
-        img[(nb * 32 + n) * CP + (chunk ^ key)] = pack_bf8(v);
+        img[(nb * 32 + n) * CP + (chunk ^ key)] = pack8<OT>(v);
       }
     }
 }
 
 // conv 3 -> 16 channels [16*grp, +16) of one point on the VALU (fp32), ReLU, -> the two chunks of k-group grp
+template <class OT = OpBf16>
 __device__ __forceinline__ void conv3_relu_chunks(float x, float y, float z, const float* __restrict__ W,
                                                   const float* __restrict__ b, int grp, u32x4* row, int key) {
   float v[16];
@@ -256,8 +300,8 @@ __device__ __forceinline__ void conv3_relu_chunks(float x, float y, float z, con
   }
   const float c0[8] = {v[0], v[1], v[2], v[3], v[8], v[9], v[10], v[11]};
   const float c1[8] = {v[4], v[5], v[6], v[7], v[12], v[13], v[14], v[15]};
-  row[(2 * grp) ^ key] = pack_bf8(c0);
-  row[(2 * grp + 1) ^ key] = pack_bf8(c1);
+  row[(2 * grp) ^ key] = pack8<OT>(c0);
+  row[(2 * grp + 1) ^ key] = pack8<OT>(c1);
 }
 
 // channel of element e of chunk c (k-slot order)
@@ -305,33 +349,33 @@ __device__ __forceinline__ void save_tile_rows_bf16(const u32x4* __restrict__ im
 // ------------------------------------------------------------------------------------------
 // a2: STN3d conv stack (pointnet.py:24-28), bf16 operands.  256 threads, 24 KiB LDS.
 // ------------------------------------------------------------------------------------------
-template <bool SAVE = false>
-__global__ __launch_bounds__(256, 2) void k_stn3d_bf(catre_points P, const float* __restrict__ W1,
-                                                     const float* __restrict__ b1, const u32x4* __restrict__ wp2,
-                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
-                                                     const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
-                                                     int M, TrainSave sv = TrainSave{}) {
-  __shared__ u32x4 smem[TP * 8 + TP * 16];
+template <bool SAVE, class OT>
+__device__ __forceinline__ void stn3d_lp(u32x4* smem, catre_points P, const float* __restrict__ W1,
+                                         const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                         const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                         const float* __restrict__ b3, float* __restrict__ pm, int B, int N, int M,
+                                         TrainSave sv) {
+  static_assert(!SAVE || !is_f16_op<OT>(), "the training (SAVE) forms are bf16-only");
   u32x4* a1 = smem;           // [64][64 ch]
   u32x4* a2 = smem + TP * 8;  // [64][128 ch]
   const int tid = threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const TileInfo ti = tile_info(blockIdx.x, B, N, M);
 
-  GemmPipeB<1, 2, false, 8, 3> g2;  // conv2 64->128: wave -> m-block `wave`
+  GemmPipeB<1, 2, false, 8, 3, 1, false, OT> g2;  // conv2 64->128: wave -> m-block `wave`
   g2.prefetch(wp2 + (wave * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, b2, wave * 32, lane);
   {
     float x, y, z;
     load_point(P, ti, lane, x, y, z);
-    conv3_relu_chunks(x, y, z, W1, b1, wave, a1 + lane * 8, bf_key<8>(lane));
+    conv3_relu_chunks<OT>(x, y, z, W1, b1, wave, a1 + lane * 8, bf_key<8>(lane));
   }
   __syncthreads();
   const size_t row0 = (ti.is_obs ? (size_t)ti.obj * N : (size_t)B * N + (size_t)ti.obj * M) + ti.p0;
   if (SAVE) save_tile_rows_bf16<64, 256, TP>(a1, sv.s1 + row0 * 32, ti.valid, tid);
   // conv3 128->1024 + max: wave owns m-blocks [8*wave, +8) in two passes of 4
-  GemmPipeB<4, 2, true, 16, 2, 1> g3a, g3b;
+  GemmPipeB<4, 2, true, 16, 2, 1, false, OT> g3a, g3b;
   float bl[2][4];
   g3a.prefetch(wp3 + ((wave * 8) * 8) * 64 + lane, 8 * 64);
   load_bias_lane<4>(bl[0], b3, (wave * 8) * 32, lane);
@@ -340,7 +384,7 @@ __global__ __launch_bounds__(256, 2) void k_stn3d_bf(catre_points P, const float
   {
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     g2.run(acc, a1, lane);
-    store_tile_bf<1, 2, true, 16>(acc, a2, wave, bv2, lane);
+    store_tile_bf<1, 2, true, 16, OT>(acc, a2, wave, bv2, lane);
   }
   __syncthreads();
   if (SAVE) save_tile_rows_bf16<128, 256, TP>(a2, sv.s2 + row0 * 64, ti.valid, tid);
@@ -369,19 +413,35 @@ __global__ __launch_bounds__(256, 2) void k_stn3d_bf(catre_points P, const float
       max_tile_store_pre<4, 2>(acc, out, (wave * 8 + 4) * 32, bl[1], true, lane);
   }
 }
+template <bool SAVE = false>
+__global__ __launch_bounds__(256, 2) void k_stn3d_bf(catre_points P, const float* __restrict__ W1,
+                                                     const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                     const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
+                                                     int M, TrainSave sv = TrainSave{}) {
+  __shared__ u32x4 smem[TP * 8 + TP * 16];
+  stn3d_lp<SAVE, OpBf16>(smem, P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sv);
+}
+__global__ __launch_bounds__(256, 2) void k_stn3d_hf(catre_points P, const float* __restrict__ W1,
+                                                     const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                     const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
+                                                     int M) {
+  __shared__ u32x4 smem[TP * 8 + TP * 16];
+  stn3d_lp<false, OpF16>(smem, P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, TrainSave{});
+}
 
 // ------------------------------------------------------------------------------------------
 // a3+a4: x T3 -> relu(conv1) -> STNkd conv stack 64->64->128->1024 (+ReLU) + per-tile max, bf16 operands.
 // ------------------------------------------------------------------------------------------
-template <bool SAVE = false>
-__global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float* __restrict__ trans3,
-                                                     const float* __restrict__ Wc1, const float* __restrict__ bc1,
-                                                     const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
-                                                     const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
-                                                     const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
-                                                     float* __restrict__ pm, int B, int N, int M,
-                                                     TrainSave sv = TrainSave{}) {
-  __shared__ u32x4 smem[2 * TP * 8 + TP * 16];
+template <bool SAVE, class OT>
+__device__ __forceinline__ void stnkd_lp(u32x4* smem, catre_points P, const float* __restrict__ trans3,
+                                         const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                         const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                         const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                         const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                         float* __restrict__ pm, int B, int N, int M, TrainSave sv) {
+  static_assert(!SAVE || !is_f16_op<OT>(), "the training (SAVE) forms are bf16-only");
   u32x4* h1 = smem;
   u32x4* f1 = smem + TP * 8;
   u32x4* f2 = smem + 2 * TP * 8;
@@ -390,7 +450,7 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
   const TileInfo ti = tile_info(blockIdx.x, B, N, M);
 
   const int mblk1 = wave >> 1, nb1 = wave & 1;
-  GemmPipeB<1, 1, false, 8, 4> g1;  // fstn.conv1 64->64: 2 m-blocks x 2 point blocks
+  GemmPipeB<1, 1, false, 8, 4, 1, false, OT> g1;  // fstn.conv1 64->64: 2 m-blocks x 2 point blocks
   g1.prefetch(wpf1 + (mblk1 * 4) * 64 + lane, 0);
   f32x4 bv1[1][4];
   load_bias_quads<1>(bv1, bf1, mblk1 * 32, lane);
@@ -398,10 +458,10 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
     float x, y, z;
     load_point(P, ti, lane, x, y, z);
     apply_t3(trans3 + ti.cloud * 9, x, y, z);
-    conv3_relu_chunks(x, y, z, Wc1, bc1, wave, h1 + lane * 8, bf_key<8>(lane));
+    conv3_relu_chunks<OT>(x, y, z, Wc1, bc1, wave, h1 + lane * 8, bf_key<8>(lane));
   }
   __syncthreads();
-  GemmPipeB<1, 2, false, 8, 3> g2;
+  GemmPipeB<1, 2, false, 8, 3, 1, false, OT> g2;
   g2.prefetch(wpf2 + (wave * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, bf2, wave * 32, lane);
@@ -409,12 +469,12 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
   {
     f32x16 acc[1][1] = {{zero16()}};
     g1.run(acc, h1 + nb1 * 32 * 8, lane);
-    store_tile_bf<1, 1, true, 8>(acc, f1 + nb1 * 32 * 8, mblk1, bv1, lane);
+    store_tile_bf<1, 1, true, 8, OT>(acc, f1 + nb1 * 32 * 8, mblk1, bv1, lane);
   }
   __syncthreads();
   const size_t row0 = (ti.is_obs ? (size_t)ti.obj * N : (size_t)B * N + (size_t)ti.obj * M) + ti.p0;
   if (SAVE) save_tile_rows_bf16<64, 256, TP>(f1, sv.s1 + row0 * 32, ti.valid, tid);
-  GemmPipeB<4, 2, true, 16, 2, 1> g3a, g3b;
+  GemmPipeB<4, 2, true, 16, 2, 1, false, OT> g3a, g3b;
   float bl[2][4];
   g3a.prefetch(wpf3 + ((wave * 8) * 8) * 64 + lane, 8 * 64);
   load_bias_lane<4>(bl[0], bf3, (wave * 8) * 32, lane);
@@ -423,7 +483,7 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
   {
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     g2.run(acc, f1, lane);
-    store_tile_bf<1, 2, true, 16>(acc, f2, wave, bv2, lane);
+    store_tile_bf<1, 2, true, 16, OT>(acc, f2, wave, bv2, lane);
   }
   __syncthreads();
   if (SAVE) save_tile_rows_bf16<128, 256, TP>(f2, sv.s2 + row0 * 64, ti.valid, tid);
@@ -452,6 +512,26 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
       max_tile_store_pre<4, 2>(acc, out, (wave * 8 + 4) * 32, bl[1], true, lane);
   }
 }
+template <bool SAVE = false>
+__global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float* __restrict__ trans3,
+                                                     const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                     const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                     const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                     const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                     float* __restrict__ pm, int B, int N, int M,
+                                                     TrainSave sv = TrainSave{}) {
+  __shared__ u32x4 smem[2 * TP * 8 + TP * 16];
+  stnkd_lp<SAVE, OpBf16>(smem, P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sv);
+}
+__global__ __launch_bounds__(256, 2) void k_stnkd_hf(catre_points P, const float* __restrict__ trans3,
+                                                     const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                     const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                     const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                     const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                     float* __restrict__ pm, int B, int N, int M) {
+  __shared__ u32x4 smem[2 * TP * 8 + TP * 16];
+  stnkd_lp<false, OpF16>(smem, P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, TrainSave{});
+}
 
 // ------------------------------------------------------------------------------------------
 // a3+a5: trunk (pointnet.py:98-116), bf16 operands.  256 threads and exactly 80 KiB of LDS so that TWO
@@ -461,15 +541,15 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf(catre_points P, const float
 //   a3 [64][512 ch] 64 KiB | a2 [64][128 ch] 16 KiB; h1 / T64 image / pointfeat image alias the a3 region.
 // pointfeat leaves as bf16 chunks [point][8] (k-slot order) - the layout the rotation head consumes.
 // ------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float* __restrict__ trans3,
-                                                     const float* __restrict__ trans64, const float* __restrict__ Wc1,
-                                                     const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
-                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
-                                                     const float* __restrict__ b3, const u32x4* __restrict__ wp4,
-                                                     const float* __restrict__ b4, float* __restrict__ pm,
-                                                     u32x4* __restrict__ pointfeat, int B, int N, int M,
-                                                     unsigned long long* __restrict__ trace) {
-  __shared__ u32x4 smem[TP * 64 + TP * 16];
+template <class OT>
+__device__ __forceinline__ void trunk_lp(u32x4* smem, catre_points P, const float* __restrict__ trans3,
+                                         const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                         const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                         const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                         const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                         const float* __restrict__ b4, float* __restrict__ pm,
+                                         u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                         unsigned long long* __restrict__ trace) {
 #define TRUNKB_STAMP(i)                                                                                    \
   do {                                                                                                     \
     if (CATRE_TRACE_ON && trace && (threadIdx.x & 63) == 0)                                                                  \
@@ -488,7 +568,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
   const int n = lane & 31, h = lane >> 5;
   TRUNKB_STAMP(0);
 
-  GemmPipeB<1, 2, false, 8, 3> g2;  // conv2 64->128: wave -> m-block `wave`, both point blocks
+  GemmPipeB<1, 2, false, 8, 3, 1, false, OT> g2;  // conv2 64->128: wave -> m-block `wave`, both point blocks
   g2.prefetch(wp2 + (wave * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, b2, wave * 32, lane);
@@ -496,7 +576,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
     float x, y, z;
     load_point(P, ti, lane, x, y, z);
     apply_t3(trans3 + ti.cloud * 9, x, y, z);
-    conv3_relu_chunks(x, y, z, Wc1, bc1, wave, (ft ? h1 : pf) + lane * 8, bf_key<8>(lane));
+    conv3_relu_chunks<OT>(x, y, z, Wc1, bc1, wave, (ft ? h1 : pf) + lane * 8, bf_key<8>(lane));
     if (ft) {  // A-operand image of the feature transform: row j holds T64[i][j] over i (pointnet.py:107-109)
       const float* src = trans64 + (size_t)ti.cloud * 4096 + (wave * 16) * 64 + lane;
       float v[16];
@@ -505,8 +585,8 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
       const float c0[8] = {v[0], v[1], v[2], v[3], v[8], v[9], v[10], v[11]};
       const float c1[8] = {v[4], v[5], v[6], v[7], v[12], v[13], v[14], v[15]};
       const int key = bf_key<8>(lane);
-      tA[lane * 8 + ((2 * wave) ^ key)] = pack_bf8(c0);
-      tA[lane * 8 + ((2 * wave + 1) ^ key)] = pack_bf8(c1);
+      tA[lane * 8 + ((2 * wave) ^ key)] = pack8<OT>(c0);
+      tA[lane * 8 + ((2 * wave + 1) ^ key)] = pack8<OT>(c1);
     }
   }
   __syncthreads();
@@ -518,16 +598,16 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
       const u32x4* ar = tA + (mblk * 32 + n) * 8;
       const u32x4* br = h1 + (nb * 32 + n) * 8;
 #pragma unroll
-      for (int kc = 0; kc < 4; ++kc) acc[0][0] = mfma_bf(ar[(2 * kc + h) ^ key], br[(2 * kc + h) ^ key], acc[0][0]);
+      for (int kc = 0; kc < 4; ++kc) acc[0][0] = OT::mfma(ar[(2 * kc + h) ^ key], br[(2 * kc + h) ^ key], acc[0][0]);
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
       const f32x4 zb[1][4] = {{z4, z4, z4, z4}};
-      store_tile_bf<1, 1, false, 8>(acc, pf + nb * 32 * 8, mblk, zb, lane);
+      store_tile_bf<1, 1, false, 8, OT>(acc, pf + nb * 32 * 8, mblk, zb, lane);
     }
     __syncthreads();
   }
   TRUNKB_STAMP(2);
   // conv3 128->512: wave owns m-blocks [4*wave, +4) in two passes of 2; first weights + bias requested now
-  GemmPipeB<2, 2, false, 16, 3, 1> g3a, g3b;
+  GemmPipeB<2, 2, false, 16, 3, 1, false, OT> g3a, g3b;
   g3a.prefetch(wp3 + ((wave * 4) * 8) * 64 + lane, 8 * 64);
   f32x4 bv3[2][4];
   load_bias_quads<2>(bv3, b3, wave * 128, lane);
@@ -539,8 +619,8 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
     float m[8];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      m[2 * i] = fmaxf(bf_lo(pfc0[i]), bf_lo(pfc1[i]));
-      m[2 * i + 1] = fmaxf(bf_hi(pfc0[i]), bf_hi(pfc1[i]));
+      m[2 * i] = fmaxf(OT::lo(pfc0[i]), OT::lo(pfc1[i]));
+      m[2 * i + 1] = fmaxf(OT::hi(pfc0[i]), OT::hi(pfc1[i]));
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -556,7 +636,7 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
   {
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     g2.run(acc, pf, lane);
-    store_tile_bf<1, 2, true, 16>(acc, a2, wave, bv2, lane);
+    store_tile_bf<1, 2, true, 16, OT>(acc, a2, wave, bv2, lane);
   }
   __syncthreads();
   float pf_max = 0.f;
@@ -569,17 +649,17 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
     for (int mb = 0; mb < 2; ++mb) acc[mb][0] = acc[mb][1] = zero16();
     g3a.run(acc, a2, lane);
     g3b.prefetch(wp3 + ((wave * 4 + 2) * 8) * 64 + lane, 8 * 64);
-    store_tile_bf<2, 2, true, 64>(acc, a3, wave * 4, bv3, lane);
+    store_tile_bf<2, 2, true, 64, OT>(acc, a3, wave * 4, bv3, lane);
     load_bias_quads<2>(bv3, b3, wave * 128 + 64, lane);
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int mb = 0; mb < 2; ++mb) acc[mb][0] = acc[mb][1] = zero16();
     g3b.run(acc, a2, lane);
-    store_tile_bf<2, 2, true, 64>(acc, a3, wave * 4 + 2, bv3, lane);
+    store_tile_bf<2, 2, true, 64, OT>(acc, a3, wave * 4 + 2, bv3, lane);
   }
   TRUNKB_STAMP(4);
   // conv4 512->1024 + max: wave owns m-blocks [8*wave, +8) in two passes of 4
-  GemmPipeB<4, 2, true, 64, 2, 1> g4a, g4b;
+  GemmPipeB<4, 2, true, 64, 2, 1, false, OT> g4a, g4b;
   g4a.prefetch(wp4 + ((wave * 8) * 32) * 64 + lane, 32 * 64);
   float bl4[2][4];
   load_bias_lane<4>(bl4[0], b4, (wave * 8) * 32, lane);
@@ -612,6 +692,28 @@ __global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float
   }
   TRUNKB_STAMP(7);
 #undef TRUNKB_STAMP
+}
+__global__ __launch_bounds__(256, 2) void k_trunk_bf(catre_points P, const float* __restrict__ trans3,
+                                                     const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                     const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                     const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                                     const float* __restrict__ b4, float* __restrict__ pm,
+                                                     u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                                     unsigned long long* __restrict__ trace) {
+  __shared__ u32x4 smem[TP * 64 + TP * 16];
+  trunk_lp<OpBf16>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace);
+}
+__global__ __launch_bounds__(256, 2) void k_trunk_hf(catre_points P, const float* __restrict__ trans3,
+                                                     const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                     const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                                     const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                     const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                                     const float* __restrict__ b4, float* __restrict__ pm,
+                                                     u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                                     unsigned long long* __restrict__ trace) {
+  __shared__ u32x4 smem[TP * 64 + TP * 16];
+  trunk_lp<OpF16>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -724,14 +826,18 @@ __device__ __forceinline__ void pair_info(int bid, int B, int N, int M, TileInfo
 // weight fragment feeds four MFMAs).  Same contraction order per output, exact maxima: the bits of k_stn3d_bf / k_stnkd_bf.
 // conv3 128 -> 1024 + ReLU + max: the wave owns m-blocks [8 wave, +8) in four passes of two.
 // ------------------------------------------------------------------------------------------
-typedef GemmPipeB<2, 4, true, 16, 3, 1, true> StnConv3Pipe;
+template <class OT = OpBf16>
+using StnConv3PipeT = GemmPipeB<2, 4, true, 16, 3, 1, true, OT>;
+typedef StnConv3PipeT<> StnConv3Pipe;
 // g[0] arrives with its first weight fragments already requested (stn_conv3_prefetch, issued by the caller BEFORE the conv2
 // phase: the L2 round trip then runs under conv2 and its barrier instead of after them)
-__device__ __forceinline__ void stn_conv3_prefetch(StnConv3Pipe (&g)[2], const u32x4* __restrict__ wp3, int wave, int lane) {
+template <class OT>
+__device__ __forceinline__ void stn_conv3_prefetch(StnConv3PipeT<OT> (&g)[2], const u32x4* __restrict__ wp3, int wave,
+                                                   int lane) {
   g[0].prefetch(wp3 + ((size_t)(wave * 8) * 8) * 64 + lane, 8 * 64);
 }
-template <bool SAVE = false>
-__device__ __forceinline__ void stn_conv3_pair_bf(StnConv3Pipe (&g)[2], const u32x4* __restrict__ wp3,
+template <bool SAVE = false, class OT = OpBf16>
+__device__ __forceinline__ void stn_conv3_pair_bf(StnConv3PipeT<OT> (&g)[2], const u32x4* __restrict__ wp3,
                                                   const float* __restrict__ b3, const u32x4* a2,
                                                   float* __restrict__ out, float* __restrict__ out2, int wave, int lane,
                                                   float* __restrict__ pmax = nullptr, int* __restrict__ pidx = nullptr,
@@ -755,13 +861,13 @@ __device__ __forceinline__ void stn_conv3_pair_bf(StnConv3Pipe (&g)[2], const u3
 
 // SAVE (training forward under autocast, N and M multiples of 64): like k_stn3d_bf<true> / k_stnkd_bf<true> - the conv1 / conv2
 // images as fp32 rows (bf16 values) and the per-tile (max, arg-max row) pairs, written to both tiles' rows of a pair.
-template <bool SAVE = false>
-__global__ __launch_bounds__(256, 2) void k_stn3d_bf2(catre_points P, const float* __restrict__ W1,
-                                                      const float* __restrict__ b1, const u32x4* __restrict__ wp2,
-                                                      const float* __restrict__ b2, const u32x4* __restrict__ wp3,
-                                                      const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
-                                                      int M, TrainSave sv = TrainSave{}) {
-  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * TP * 8];
+template <bool SAVE, class OT>
+__device__ __forceinline__ void stn3d_lp2(u32x4* smem, catre_points P, const float* __restrict__ W1,
+                                          const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                          const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                          const float* __restrict__ b3, float* __restrict__ pm, int B, int N, int M,
+                                          TrainSave sv) {
+  static_assert(!SAVE || !is_f16_op<OT>(), "the training (SAVE) forms are bf16-only");
   u32x4* a2 = smem;                // [128][128 ch] (first: its rows are the XOR-addressed ones)
   u32x4* a1 = smem + 2 * TP * 16;  // [128][64 ch]
   const int tid = threadIdx.x, lane = tid & 63;
@@ -770,7 +876,7 @@ __global__ __launch_bounds__(256, 2) void k_stn3d_bf2(catre_points P, const floa
   int tile0;
   pair_info(blockIdx.x, B, N, M, ti, tile0);
 
-  GemmPipeB<1, 4, false, 8, 3> g2;  // conv2 64->128: wave -> m-block `wave`, all four point blocks
+  GemmPipeB<1, 4, false, 8, 3, 1, false, OT> g2;  // conv2 64->128: wave -> m-block `wave`, all four point blocks
   g2.prefetch(wp2 + (wave * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, b2, wave * 32, lane);
@@ -778,38 +884,55 @@ __global__ __launch_bounds__(256, 2) void k_stn3d_bf2(catre_points P, const floa
     const int p = (wave & 1) * TP + lane, g0 = (wave >> 1) * 2;
     float x, y, z;
     load_point(P, ti, p, x, y, z);
-    conv3_relu_chunks(x, y, z, W1, b1, g0, a1 + p * 8, bf_key<8>(p));
-    conv3_relu_chunks(x, y, z, W1, b1, g0 + 1, a1 + p * 8, bf_key<8>(p));
+    conv3_relu_chunks<OT>(x, y, z, W1, b1, g0, a1 + p * 8, bf_key<8>(p));
+    conv3_relu_chunks<OT>(x, y, z, W1, b1, g0 + 1, a1 + p * 8, bf_key<8>(p));
   }
   __syncthreads();
   const size_t row0 = (ti.is_obs ? (size_t)ti.obj * N : (size_t)B * N + (size_t)ti.obj * M) + ti.p0;
   if (SAVE) save_tile_rows_bf16<64, 256, 2 * TP>(a1, sv.s1 + row0 * 32, ti.valid, tid);
-  StnConv3Pipe g3[2];
+  StnConv3PipeT<OT> g3[2];
   stn_conv3_prefetch(g3, wp3, wave, lane);
   {
     f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
     g2.run(acc, a1, lane);
-    store_tile_bf<1, 4, true, 16>(acc, a2, wave, bv2, lane);
+    store_tile_bf<1, 4, true, 16, OT>(acc, a2, wave, bv2, lane);
   }
   __syncthreads();
   if (SAVE) save_tile_rows_bf16<128, 256, 2 * TP>(a2, sv.s2 + row0 * 64, ti.valid, tid);
   float* out = pm + (size_t)tile0 * PMW;
   if constexpr (SAVE)
-    stn_conv3_pair_bf<true>(g3, wp3, b3, a2, out, nullptr, wave, lane, sv.pmax + (size_t)tile0 * 1024,
+    stn_conv3_pair_bf<true, OT>(g3, wp3, b3, a2, out, nullptr, wave, lane, sv.pmax + (size_t)tile0 * 1024,
                             sv.pidx + (size_t)tile0 * 1024, ti.valid > TP, (int)row0);
   else
-    stn_conv3_pair_bf(g3, wp3, b3, a2, out, ti.valid > TP ? out + PMW : nullptr, wave, lane);
+    stn_conv3_pair_bf<false, OT>(g3, wp3, b3, a2, out, ti.valid > TP ? out + PMW : nullptr, wave, lane);
+}
+template <bool SAVE = false>
+__global__ __launch_bounds__(256, 2) void k_stn3d_bf2(catre_points P, const float* __restrict__ W1,
+                                                      const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                                      const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                      const float* __restrict__ b3, float* __restrict__ pm, int B,
+                                                      int N, int M, TrainSave sv = TrainSave{}) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * TP * 8];
+  stn3d_lp2<SAVE, OpBf16>(smem, P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sv);
+}
+__global__ __launch_bounds__(256, 2) void k_stn3d_hf2(catre_points P, const float* __restrict__ W1,
+                                                      const float* __restrict__ b1, const u32x4* __restrict__ wp2,
+                                                      const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                      const float* __restrict__ b3, float* __restrict__ pm, int B,
+                                                      int N, int M) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * TP * 8];
+  stn3d_lp2<false, OpF16>(smem, P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, TrainSave{});
 }
 
-template <bool SAVE = false>
-__global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const float* __restrict__ trans3,
-                                                      const float* __restrict__ Wc1, const float* __restrict__ bc1,
-                                                      const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
-                                                      const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
-                                                      const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
-                                                      float* __restrict__ pm, int B, int N, int M,
-                                                      TrainSave sv = TrainSave{}) {
-  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * 2 * TP * 8];
+
+template <bool SAVE, class OT>
+__device__ __forceinline__ void stnkd_lp2(u32x4* smem, catre_points P, const float* __restrict__ trans3,
+                                          const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                          const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                          const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                          const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                          float* __restrict__ pm, int B, int N, int M, TrainSave sv) {
+  static_assert(!SAVE || !is_f16_op<OT>(), "the training (SAVE) forms are bf16-only");
   u32x4* f2 = smem;                              // [128][128 ch]
   u32x4* h1 = smem + 2 * TP * 16;                // [128][64 ch]
   u32x4* f1 = smem + 2 * TP * 16 + 2 * TP * 8;   // [128][64 ch]
@@ -820,7 +943,7 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const floa
   pair_info(blockIdx.x, B, N, M, ti, tile0);
 
   const int mblk1 = wave >> 1, half1 = wave & 1;
-  GemmPipeB<1, 2, false, 8, 4> g1;  // fstn.conv1 64->64: 2 m-blocks x 4 point blocks, (m-block, point half) per wave
+  GemmPipeB<1, 2, false, 8, 4, 1, false, OT> g1;  // fstn.conv1 64->64: 2 m-blocks x 4 point blocks, (m-block, point half) per wave
   g1.prefetch(wpf1 + (mblk1 * 4) * 64 + lane, 0);
   f32x4 bv1[1][4];
   load_bias_quads<1>(bv1, bf1, mblk1 * 32, lane);
@@ -829,11 +952,11 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const floa
     float x, y, z;
     load_point(P, ti, p, x, y, z);
     apply_t3(trans3 + ti.cloud * 9, x, y, z);
-    conv3_relu_chunks(x, y, z, Wc1, bc1, g0, h1 + p * 8, bf_key<8>(p));
-    conv3_relu_chunks(x, y, z, Wc1, bc1, g0 + 1, h1 + p * 8, bf_key<8>(p));
+    conv3_relu_chunks<OT>(x, y, z, Wc1, bc1, g0, h1 + p * 8, bf_key<8>(p));
+    conv3_relu_chunks<OT>(x, y, z, Wc1, bc1, g0 + 1, h1 + p * 8, bf_key<8>(p));
   }
   __syncthreads();
-  GemmPipeB<1, 4, false, 8, 3> g2;
+  GemmPipeB<1, 4, false, 8, 3, 1, false, OT> g2;
   g2.prefetch(wpf2 + (wave * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, bf2, wave * 32, lane);
@@ -841,27 +964,48 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const floa
   {
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     g1.run(acc, h1 + half1 * TP * 8, lane);
-    store_tile_bf<1, 2, true, 8>(acc, f1 + half1 * TP * 8, mblk1, bv1, lane);
+    store_tile_bf<1, 2, true, 8, OT>(acc, f1 + half1 * TP * 8, mblk1, bv1, lane);
   }
   __syncthreads();
   const size_t row0 = (ti.is_obs ? (size_t)ti.obj * N : (size_t)B * N + (size_t)ti.obj * M) + ti.p0;
   if (SAVE) save_tile_rows_bf16<64, 256, 2 * TP>(f1, sv.s1 + row0 * 32, ti.valid, tid);
-  StnConv3Pipe g3[2];
+  StnConv3PipeT<OT> g3[2];
   stn_conv3_prefetch(g3, wpf3, wave, lane);
   {
     f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
     g2.run(acc, f1, lane);
-    store_tile_bf<1, 4, true, 16>(acc, f2, wave, bv2, lane);
+    store_tile_bf<1, 4, true, 16, OT>(acc, f2, wave, bv2, lane);
   }
   __syncthreads();
   if (SAVE) save_tile_rows_bf16<128, 256, 2 * TP>(f2, sv.s2 + row0 * 64, ti.valid, tid);
   float* out = pm + (size_t)tile0 * PMW;
   if constexpr (SAVE)
-    stn_conv3_pair_bf<true>(g3, wpf3, bf3, f2, out, nullptr, wave, lane, sv.pmax + (size_t)tile0 * 1024,
+    stn_conv3_pair_bf<true, OT>(g3, wpf3, bf3, f2, out, nullptr, wave, lane, sv.pmax + (size_t)tile0 * 1024,
                             sv.pidx + (size_t)tile0 * 1024, ti.valid > TP, (int)row0);
   else
-    stn_conv3_pair_bf(g3, wpf3, bf3, f2, out, ti.valid > TP ? out + PMW : nullptr, wave, lane);
+    stn_conv3_pair_bf<false, OT>(g3, wpf3, bf3, f2, out, ti.valid > TP ? out + PMW : nullptr, wave, lane);
 }
+template <bool SAVE = false>
+__global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const float* __restrict__ trans3,
+                                                      const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                      const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                      const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                      const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                      float* __restrict__ pm, int B, int N, int M,
+                                                      TrainSave sv = TrainSave{}) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * 2 * TP * 8];
+  stnkd_lp2<SAVE, OpBf16>(smem, P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sv);
+}
+__global__ __launch_bounds__(256, 2) void k_stnkd_hf2(catre_points P, const float* __restrict__ trans3,
+                                                      const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                      const u32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                      const u32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                      const u32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                      float* __restrict__ pm, int B, int N, int M) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[2 * TP * 16 + 2 * 2 * TP * 8];
+  stnkd_lp2<false, OpF16>(smem, P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, TrainSave{});
+}
+
 
 #define TRUNKB2_SMEM (2 * TP * 64 + 2 * TP * 16)
 #ifndef CATRE_BF2_PFD
@@ -870,16 +1014,16 @@ __global__ __launch_bounds__(256, 2) void k_stnkd_bf2(catre_points P, const floa
 // SAVE (training forward under autocast, catre_train_trunk_fwd): additionally writes the fp32 rows the layer-wise backward
 // reads - x1 = x T3 (sv.s1, [rows,8]), h1 (sv.s2), conv2 / conv3 outputs (sv.s3, sv.s4), pointfeat (sv.s5, [rows,64]; the
 // bf16 `pointfeat` buffer is then not written) - and the per-tile (max, arg-max row) pairs instead of the maxima.
-template <bool SAVE = false>
-__global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* __restrict__ trans3,
-                                                   const float* __restrict__ trans64, const float* __restrict__ Wc1,
-                                                   const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
-                                                   const float* __restrict__ b2, const u32x4* __restrict__ wp3,
-                                                   const float* __restrict__ b3, const u32x4* __restrict__ wp4,
-                                                   const float* __restrict__ b4, float* __restrict__ pm,
-                                                   u32x4* __restrict__ pointfeat, int B, int N, int M,
-                                                   unsigned long long* __restrict__ trace, TrainSave sv = TrainSave{}) {
-  __shared__ __attribute__((aligned(1024))) u32x4 smem[TRUNKB2_SMEM];
+template <bool SAVE, class OT>
+__device__ __forceinline__ void trunk_lp2(u32x4* smem, catre_points P, const float* __restrict__ trans3,
+                                          const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                          const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                          const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                          const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                          const float* __restrict__ b4, float* __restrict__ pm,
+                                          u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                          unsigned long long* __restrict__ trace, TrainSave sv) {
+  static_assert(!SAVE || !is_f16_op<OT>(), "the training (SAVE) forms are bf16-only");
 #define TRUNKB2_STAMP(i)                                                                                   \
   do {                                                                                                     \
     if (CATRE_TRACE_ON && trace && (threadIdx.x & 63) == 0)                                                \
@@ -903,7 +1047,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
   TRUNKB2_STAMP(0);
 
   const int ph = wave >> 2, w4 = wave & 3;  // point half / quarter-of-the-channels roles of the prologue
-  GemmPipeB<1, 2, false, 8, 3> g2;          // conv2 64->128: wave -> m-block w4, the two point blocks of half ph
+  GemmPipeB<1, 2, false, 8, 3, 1, false, OT> g2;          // conv2 64->128: wave -> m-block w4, the two point blocks of half ph
   g2.prefetch(wp2 + (w4 * 4) * 64 + lane, 0);
   f32x4 bv2[1][4];
   load_bias_quads<1>(bv2, b2, w4 * 32, lane);
@@ -918,7 +1062,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
       *reinterpret_cast<f32x4*>(sv.s1 + r * 8) = lo;
       *reinterpret_cast<f32x4*>(sv.s1 + r * 8 + 4) = hi;
     }
-    conv3_relu_chunks(x, y, z, Wc1, bc1, w4, (ft ? h1 : pf) + p * 8, bf_key<8>(p));
+    conv3_relu_chunks<OT>(x, y, z, Wc1, bc1, w4, (ft ? h1 : pf) + p * 8, bf_key<8>(p));
     if (ft) {  // A-operand image of the feature transform: row j holds T64[i][j] over i (pointnet.py:107-109);
                // wave (G = w4, s = ph) fills chunk 2G+s: i = 16G + {4s..4s+3, 8+4s..8+4s+3}
       const float* src = trans64 + (size_t)ti.cloud * 4096 + (w4 * 16 + 4 * ph) * 64 + lane;
@@ -928,7 +1072,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
         v[r] = src[r * 64];
         v[4 + r] = src[(8 + r) * 64];
       }
-      tA[lane * 8 + ((2 * w4 + ph) ^ bf_key<8>(lane))] = pack_bf8(v);
+      tA[lane * 8 + ((2 * w4 + ph) ^ bf_key<8>(lane))] = pack8<OT>(v);
     }
   }
   __syncthreads();
@@ -940,10 +1084,10 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
       const u32x4* ar = tA + (mblk * 32 + n) * 8;
       const u32x4* br = h1 + (nb * 32 + n) * 8;
 #pragma unroll
-      for (int kc = 0; kc < 4; ++kc) acc[0][0] = mfma_bf(ar[(2 * kc + h) ^ key], br[(2 * kc + h) ^ key], acc[0][0]);
+      for (int kc = 0; kc < 4; ++kc) acc[0][0] = OT::mfma(ar[(2 * kc + h) ^ key], br[(2 * kc + h) ^ key], acc[0][0]);
       const f32x4 z4 = {0.f, 0.f, 0.f, 0.f};
       const f32x4 zb[1][4] = {{z4, z4, z4, z4}};
-      store_tile_bf<1, 1, false, 8>(acc, pf + nb * 32 * 8, mblk, zb, lane);
+      store_tile_bf<1, 1, false, 8, OT>(acc, pf + nb * 32 * 8, mblk, zb, lane);
     }
     __syncthreads();
   }
@@ -954,7 +1098,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
     save_tile_rows_bf<64, 512, 2 * TP>(pf, sv.s5 + srow0 * 64, ti.valid, tid);
   }
   // conv3 128->512: wave owns m-blocks [2*wave, +2) over all four point blocks; first weights + bias requested now
-  GemmPipeB<2, 4, false, 16, 2, 1> g3;
+  GemmPipeB<2, 4, false, 16, 2, 1, false, OT> g3;
   g3.prefetch(wp3 + ((wave * 2) * 8) * 64 + lane, 8 * 64);
   f32x4 bv3[2][4];
   load_bias_quads<2>(bv3, b3, wave * 64, lane);
@@ -966,8 +1110,8 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
     float m[8];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      m[2 * i] = fmaxf(bf_lo(pfc0[i]), bf_lo(pfc1[i]));
-      m[2 * i + 1] = fmaxf(bf_hi(pfc0[i]), bf_hi(pfc1[i]));
+      m[2 * i] = fmaxf(OT::lo(pfc0[i]), OT::lo(pfc1[i]));
+      m[2 * i + 1] = fmaxf(OT::hi(pfc0[i]), OT::hi(pfc1[i]));
     }
 #pragma unroll
     for (int e = 0; e < 8; ++e) {
@@ -983,7 +1127,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
   {
     f32x16 acc[1][2] = {{zero16(), zero16()}};
     g2.run(acc, pf + ph * TP * 8, lane);
-    store_tile_bf<1, 2, true, 16>(acc, a2 + ph * TP * 16, w4, bv2, lane);
+    store_tile_bf<1, 2, true, 16, OT>(acc, a2 + ph * TP * 16, w4, bv2, lane);
   }
   __syncthreads();
   float pf_max = 0.f;
@@ -1009,7 +1153,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
     }
   }
   // conv4 512->1024 + max: wave owns m-blocks [4*wave, +4) in two passes of 2 x 4 point blocks
-  GemmPipeB<2, 4, true, 64, SAVE ? 3 : CATRE_BF2_PFD, 1, true> g4a, g4b;  // SAVE: the arg-max epilogue needs the registers of one ring slot
+  GemmPipeB<2, 4, true, 64, SAVE ? 3 : CATRE_BF2_PFD, 1, true, OT> g4a, g4b;  // SAVE: the arg-max epilogue needs the registers of one ring slot
 #ifdef CATRE_DEBUG_TRACE
   g4a.ablate = g4b.ablate = __builtin_amdgcn_readfirstlane(g_ablate);
 #endif
@@ -1020,7 +1164,7 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
 #pragma unroll
       for (int nb = 0; nb < 4; ++nb) acc[mb][nb] = zero16();
     g3.run(acc, a2, lane);
-    store_tile_bf<2, 4, true, 64>(acc, a3, wave * 2, bv3, lane);
+    store_tile_bf<2, 4, true, 64, OT>(acc, a3, wave * 2, bv3, lane);
   }
   __builtin_amdgcn_sched_barrier(0);
   g4a.prefetch(wp4 + ((wave * 4) * 32) * 64 + lane, 32 * 64);  // in flight across the barrier
@@ -1068,6 +1212,29 @@ __global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* 
   TRUNKB2_STAMP(7);
 #undef TRUNKB2_STAMP
 }
+template <bool SAVE = false>
+__global__ __launch_bounds__(512) void k_trunk_bf2(catre_points P, const float* __restrict__ trans3,
+                                                   const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                   const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                                   const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                   const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                                   const float* __restrict__ b4, float* __restrict__ pm,
+                                                   u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                                   unsigned long long* __restrict__ trace, TrainSave sv = TrainSave{}) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[TRUNKB2_SMEM];
+  trunk_lp2<SAVE, OpBf16>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace, sv);
+}
+__global__ __launch_bounds__(512) void k_trunk_hf2(catre_points P, const float* __restrict__ trans3,
+                                                   const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                   const float* __restrict__ bc1, const u32x4* __restrict__ wp2,
+                                                   const float* __restrict__ b2, const u32x4* __restrict__ wp3,
+                                                   const float* __restrict__ b3, const u32x4* __restrict__ wp4,
+                                                   const float* __restrict__ b4, float* __restrict__ pm,
+                                                   u32x4* __restrict__ pointfeat, int B, int N, int M,
+                                                   unsigned long long* __restrict__ trace) {
+  __shared__ __attribute__((aligned(1024))) u32x4 smem[TRUNKB2_SMEM];
+  trunk_lp2<false, OpF16>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace, TrainSave{});
+}
 
 // ------------------------------------------------------------------------------------------
 // a9: rotation heads, bf16 operands: the structure of k_rot_l1 / k_rot_out (GN0 statistics: k_pf_moments_bf, catre_gram.h).
@@ -1088,14 +1255,14 @@ __device__ __forceinline__ void load_pf_tile_bf(const u32x4* __restrict__ pointf
 #endif
 #define ROTBF_PITCH 80                       // bytes per stage row: 32 points x 2 bytes + 16 (conflict-free 8-byte writes)
 #define ROTBF_STAGE (32 * ROTBF_PITCH / 16)  // u32x4 per wave: one 32-channel x 32-point block
-__global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ pointfeat,
-                                                      const u32x4* __restrict__ wpl0x, const u32x4* __restrict__ wpl0y,
-                                                      const float* __restrict__ aff0 /*[B*2][2][2][256]*/,
-                                                      const u32x4* __restrict__ wpl1x, const u32x4* __restrict__ wpl1y,
-                                                      const float* __restrict__ b1x, const float* __restrict__ b1y,
-                                                      unsigned short* __restrict__ y1, float* __restrict__ gn1, int B,
-                                                      int N, int M, unsigned long long* __restrict__ trace = nullptr) {
-  __shared__ u32x4 smem[TP * 8 + TP * 32 + 4 * ROTBF_STAGE];
+template <class OT>
+__device__ __forceinline__ void rot_l1_lp(u32x4* smem, const u32x4* __restrict__ pointfeat,
+                                          const u32x4* __restrict__ wpl0x, const u32x4* __restrict__ wpl0y,
+                                          const float* __restrict__ aff0 /*[B*2][2][2][256]*/,
+                                          const u32x4* __restrict__ wpl1x, const u32x4* __restrict__ wpl1y,
+                                          const float* __restrict__ b1x, const float* __restrict__ b1y,
+                                          unsigned short* __restrict__ y1, float* __restrict__ gn1, int B, int N, int M,
+                                          unsigned long long* __restrict__ trace) {
   int stamp_i = 0;
 #define ROTB_STAMP()                                                                                     \
   do {                                                                                                   \
@@ -1122,7 +1289,7 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ 
   const int n = lane & 31, h = lane >> 5;
 #pragma unroll 1
   for (int hd = 0; hd < 2; ++hd) {
-    GemmPipeB<2, 2, true, 32, ROTBF_PFD1> g1;
+    GemmPipeB<2, 2, true, 32, ROTBF_PFD1, 1, false, OT> g1;
     {
       // wave -> channels [wave*64, +64) = m-blocks 2*wave, 2*wave+1
       const float* af = aff0 + ((((size_t)rt.obj * 2 + hd) * 2 + (rt.is_obs ? 0 : 1)) * 2) * 256 + wave * 64 + 4 * h;
@@ -1136,7 +1303,7 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ 
       f32x16 acc[2][2];
 #pragma unroll
       for (int mb = 0; mb < 2; ++mb) acc[mb][0] = acc[mb][1] = zero16();
-      GemmPipeB<2, 2, false, 8, 2> g0;
+      GemmPipeB<2, 2, false, 8, 2, 1, false, OT> g0;
       g0.prefetch((hd ? wpl0y : wpl0x) + (wave * 2 * 4) * 64 + lane, 4 * 64);
       if (!(abl & 64)) g0.run(acc, pf, lane);
       ROTB_STAMP();
@@ -1169,7 +1336,7 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ 
           } else {  // quads g-1 and g complete chunk 4*(2*wave+mb) + 2*(g>>1) + h
             const float v[8] = {zprev[nb][0], zprev[nb][1], zprev[nb][2], zprev[nb][3], z[0], z[1], z[2], z[3]};
             const int chunk = 4 * (2 * wave + mb) + 2 * (g >> 1) + h;
-            a0[(nb * 32 + n) * 32 + (chunk ^ key)] = pack_bf8(v);
+            a0[(nb * 32 + n) * 32 + (chunk ^ key)] = pack8<OT>(v);
           }
         }
       }
@@ -1207,8 +1374,8 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ 
             unsigned* srow = stage + n * (ROTBF_PITCH / 4) + 2 * h;
 #pragma unroll
             for (int g = 0; g < 4; ++g) {
-              const u32x2 d = {pack_bf2(acc[mb][nb][4 * g], acc[mb][nb][4 * g + 1]),
-                               pack_bf2(acc[mb][nb][4 * g + 2], acc[mb][nb][4 * g + 3])};
+              const u32x2 d = {OT::pack2(acc[mb][nb][4 * g], acc[mb][nb][4 * g + 1]),
+                               OT::pack2(acc[mb][nb][4 * g + 2], acc[mb][nb][4 * g + 3])};
               *reinterpret_cast<u32x2*>(srow + 4 * g) = d;
             }
             const u32x4* sv = reinterpret_cast<const u32x4*>(stage);
@@ -1274,21 +1441,42 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ 
   }
 #undef ROTB_STAMP
 }
+__global__ __launch_bounds__(256, 2) void k_rot_l1_bf(const u32x4* __restrict__ pointfeat,
+                                                      const u32x4* __restrict__ wpl0x, const u32x4* __restrict__ wpl0y,
+                                                      const float* __restrict__ aff0 /*[B*2][2][2][256]*/,
+                                                      const u32x4* __restrict__ wpl1x, const u32x4* __restrict__ wpl1y,
+                                                      const float* __restrict__ b1x, const float* __restrict__ b1y,
+                                                      unsigned short* __restrict__ y1, float* __restrict__ gn1, int B,
+                                                      int N, int M, unsigned long long* __restrict__ trace = nullptr) {
+  __shared__ u32x4 smem[TP * 8 + TP * 32 + 4 * ROTBF_STAGE];
+  rot_l1_lp<OpBf16>(smem, pointfeat, wpl0x, wpl0y, aff0, wpl1x, wpl1y, b1x, b1y, y1, gn1, B, N, M, trace);
+}
+__global__ __launch_bounds__(256, 2) void k_rot_l1_hf(const u32x4* __restrict__ pointfeat,
+                                                      const u32x4* __restrict__ wpl0x, const u32x4* __restrict__ wpl0y,
+                                                      const float* __restrict__ aff0 /*[B*2][2][2][256]*/,
+                                                      const u32x4* __restrict__ wpl1x, const u32x4* __restrict__ wpl1y,
+                                                      const float* __restrict__ b1x, const float* __restrict__ b1y,
+                                                      unsigned short* __restrict__ y1, float* __restrict__ gn1, int B,
+                                                      int N, int M, unsigned long long* __restrict__ trace = nullptr) {
+  __shared__ u32x4 smem[TP * 8 + TP * 32 + 4 * ROTBF_STAGE];
+  rot_l1_lp<OpF16>(smem, pointfeat, wpl0x, wpl0y, aff0, wpl1x, wpl1y, b1x, b1y, y1, gn1, B, N, M, trace);
+}
+
 
 // GN1 -> GELU -> neck (256->3) -> conv_p weighted sum over the tile's points; reads the bf16 y1 in the block order
 // k_rot_l1_bf writes ([2 point halves][256 channels][32 points] per tile and head).  A lane takes 8 consecutive points
 // (16 bytes) of 4 channels in both halves: every load instruction of the workgroup is 4 KiB of consecutive bytes, the conv_p
 // weights of its 16 points stay in registers, and the neck is applied to the per-channel sums (sum_p w_p gelu(z_cp))
 // instead of to every point.
-__global__ __launch_bounds__(256) void k_rot_out_bf(const unsigned short* __restrict__ y1,
-                                                    const float* __restrict__ gn1stat, const float* __restrict__ gam1x,
-                                                    const float* __restrict__ bet1x, const float* __restrict__ gam1y,
-                                                    const float* __restrict__ bet1y, const float* __restrict__ neckx,
-                                                    const float* __restrict__ necky, const float* __restrict__ wpx,
-                                                    const float* __restrict__ wpy, float* __restrict__ rpart, int B,
-                                                    int N, int M, int rd) {
-  __shared__ float cst[5][256];  // per channel: GN1 scale, shift, the three neck weights
-  __shared__ float red[4][4];
+template <class OT>
+__device__ __forceinline__ void rot_out_lp(float (*cst)[256] /*[5][256]*/, float (*red)[4] /*[4][4]*/,
+                                           const unsigned short* __restrict__ y1, const float* __restrict__ gn1stat,
+                                           const float* __restrict__ gam1x, const float* __restrict__ bet1x,
+                                           const float* __restrict__ gam1y, const float* __restrict__ bet1y,
+                                           const float* __restrict__ neckx, const float* __restrict__ necky,
+                                           const float* __restrict__ wpx, const float* __restrict__ wpy,
+                                           float* __restrict__ rpart, int B, int N, int M, int rd) {
+  // cst: per channel GN1 scale, shift, the three neck weights
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int T = (N + TP - 1) / TP + (M + TP - 1) / TP;
   const int hd = blockIdx.y;
@@ -1336,12 +1524,12 @@ __global__ __launch_bounds__(256) void k_rot_out_bf(const unsigned short* __rest
     for (int nb = 0; nb < 2; ++nb) {
       const u32x4 u = rows[nb * 4 + k];
       float z[4];
-      gelu_affine4_lp(bf_lo(u[0]), bf_hi(u[0]), bf_lo(u[1]), bf_hi(u[1]), sc, sh, z);
+      gelu_affine4_lp(OT::lo(u[0]), OT::hi(u[0]), OT::lo(u[1]), OT::hi(u[1]), sc, sh, z);
       t = fmaf(w[nb][0], z[0], t);
       t = fmaf(w[nb][1], z[1], t);
       t = fmaf(w[nb][2], z[2], t);
       t = fmaf(w[nb][3], z[3], t);
-      gelu_affine4_lp(bf_lo(u[2]), bf_hi(u[2]), bf_lo(u[3]), bf_hi(u[3]), sc, sh, z);
+      gelu_affine4_lp(OT::lo(u[2]), OT::hi(u[2]), OT::lo(u[3]), OT::hi(u[3]), sc, sh, z);
       t = fmaf(w[nb][4], z[0], t);
       t = fmaf(w[nb][5], z[1], t);
       t = fmaf(w[nb][6], z[2], t);
@@ -1361,4 +1549,26 @@ __global__ __launch_bounds__(256) void k_rot_out_bf(const unsigned short* __rest
   if (tid < 3) {
     rpart[(((size_t)rt.obj * 2 + hd) * T + rt.t) * 4 + tid] = red[0][tid] + red[1][tid] + red[2][tid] + red[3][tid];
   }
+}
+__global__ __launch_bounds__(256) void k_rot_out_bf(const unsigned short* __restrict__ y1,
+                                                    const float* __restrict__ gn1stat, const float* __restrict__ gam1x,
+                                                    const float* __restrict__ bet1x, const float* __restrict__ gam1y,
+                                                    const float* __restrict__ bet1y, const float* __restrict__ neckx,
+                                                    const float* __restrict__ necky, const float* __restrict__ wpx,
+                                                    const float* __restrict__ wpy, float* __restrict__ rpart, int B,
+                                                    int N, int M, int rd) {
+  __shared__ float cst[5][256];
+  __shared__ float red[4][4];
+  rot_out_lp<OpBf16>(cst, red, y1, gn1stat, gam1x, bet1x, gam1y, bet1y, neckx, necky, wpx, wpy, rpart, B, N, M, rd);
+}
+__global__ __launch_bounds__(256) void k_rot_out_hf(const unsigned short* __restrict__ y1,
+                                                    const float* __restrict__ gn1stat, const float* __restrict__ gam1x,
+                                                    const float* __restrict__ bet1x, const float* __restrict__ gam1y,
+                                                    const float* __restrict__ bet1y, const float* __restrict__ neckx,
+                                                    const float* __restrict__ necky, const float* __restrict__ wpx,
+                                                    const float* __restrict__ wpy, float* __restrict__ rpart, int B,
+                                                    int N, int M, int rd) {
+  __shared__ float cst[5][256];
+  __shared__ float red[4][4];
+  rot_out_lp<OpF16>(cst, red, y1, gn1stat, gam1x, bet1x, gam1y, bet1y, neckx, necky, wpx, wpy, rpart, B, N, M, rd);
 }

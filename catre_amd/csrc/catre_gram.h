@@ -38,9 +38,10 @@
 // workgroups per cloud of k_pf_moments (gridDim.y): the four tile groups on four workgroups, or one workgroup for all
 inline int pf_groups(int B) { return (PF_SPLIT_ALWAYS || 2 * B * PF_NG <= 256) ? PF_NG : 1; }
 // body for cloud `cloud`, tile group by of gy (gy == 1: all four groups); 256 threads
-// BF: pointfeat is the bf16 point-major buffer of the reduced-precision path ([point][8 chunks of 8 bf16], channels in
-// k-slot order inside a chunk - catre_bf16.h); a thread then stages chunk tid & 7 of rows tid >> 3 and (tid >> 3) + 32.
-template <bool BF = false>
+// BF: pointfeat is the bf16 (OT = OpF16: fp16) point-major buffer of the reduced-precision path ([point][8 chunks of 8
+// values], channels in k-slot order inside a chunk - catre_bf16.h); a thread then stages chunk tid & 7 of rows tid >> 3
+// and (tid >> 3) + 32.
+template <bool BF = false, class OT = OpBf16>
 __device__ __forceinline__ void pf_moments_body(const float* __restrict__ pointfeat,
                                                 float* __restrict__ Gc /*[2B][PF_NG][4096]*/,
                                                 float* __restrict__ s1c /*[2B][PF_NG][64]*/,
@@ -82,8 +83,8 @@ __device__ __forceinline__ void pf_moments_body(const float* __restrict__ pointf
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const bool ok = !mask || t * TP + rb + 32 * u < n;
-        const f32x4 a = {bf_lo(nxb[u][0]), bf_hi(nxb[u][0]), bf_lo(nxb[u][1]), bf_hi(nxb[u][1])};
-        const f32x4 b = {bf_lo(nxb[u][2]), bf_hi(nxb[u][2]), bf_lo(nxb[u][3]), bf_hi(nxb[u][3])};
+        const f32x4 a = {OT::lo(nxb[u][0]), OT::hi(nxb[u][0]), OT::lo(nxb[u][1]), OT::hi(nxb[u][1])};
+        const f32x4 b = {OT::lo(nxb[u][2]), OT::hi(nxb[u][2]), OT::lo(nxb[u][3]), OT::hi(nxb[u][3])};
         *reinterpret_cast<f32x4*>(buf + (rb + 32 * u) * LD64 + chb) = ok ? a - sa : z;
         *reinterpret_cast<f32x4*>(buf + (rb + 32 * u) * LD64 + chb + 8) = ok ? b - sb : z;
       }
@@ -165,6 +166,14 @@ __global__ __launch_bounds__(256) void k_pf_moments_bf(const u32x4* __restrict__
   __shared__ __attribute__((aligned(16))) float lds[PF_MOM_SMEM];
   pf_moments_body<true>(reinterpret_cast<const float*>(pointfeat), Gc, s1c, shc, B, N, M, blockIdx.x, blockIdx.y,
                         gridDim.y, lds);
+}
+// ... and from the fp16 pointfeat buffer (COMPUTE_DTYPE="fp16")
+__global__ __launch_bounds__(256) void k_pf_moments_hf(const u32x4* __restrict__ pointfeat, float* __restrict__ Gc,
+                                                       float* __restrict__ s1c, float* __restrict__ shc, int B, int N,
+                                                       int M) {
+  __shared__ __attribute__((aligned(16))) float lds[PF_MOM_SMEM];
+  pf_moments_body<true, OpF16>(reinterpret_cast<const float*>(pointfeat), Gc, s1c, shc, B, N, M, blockIdx.x, blockIdx.y,
+                               gridDim.y, lds);
 }
 
 // aff [B*2 (object, head)][2 (observed, prior)][2 (sc, sh)][256]: gelu_in = acc * sc + sh with sc = rstd * gamma,

@@ -1537,8 +1537,10 @@ __global__ __launch_bounds__(256) void k_colmax(const float* __restrict__ x, flo
 // every bf16 (or hi + lo split) fragment pack of a weight image in ONE launch (k_pack_frag_multi's job table; the
 // per-element arithmetic is k_pack_frag_bf's / k_pack_frag_split's): a training step re-packs the image after every
 // optimizer step, and twelve 3-us launches sat on the critical path of each autocast / split iteration
-template <bool SPLIT>
-__global__ void k_pack_frag_lp_multi(PackJobs J) {
+// OT = OpF16: the fp16 packs of the same matrices (k_pack_frag_hf_multi; no split kind)
+template <bool SPLIT, class OT = OpBf16>
+__device__ __forceinline__ void pack_frag_lp_body(const PackJobs& J) {
+  static_assert(!SPLIT || !is_f16_op<OT>(), "the split packs are bf16 pairs");
   const int gi = blockIdx.x * blockDim.x + threadIdx.x;
   if (gi >= J.end[J.n - 1]) return;
   int j = 0;
@@ -1551,10 +1553,15 @@ __global__ void k_pack_frag_lp_multi(PackJobs J) {
   const int row = mb * 32 + (lane & 31), col = kc * 16 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
   const float w = J.src[j][(size_t)row * J.ld[j] + J.coloff[j] + col];
   unsigned short* dst = reinterpret_cast<unsigned short*>(J.dst[j]);
-  const __bf16 h = (__bf16)w;
+  const typename OT::T h = (typename OT::T)w;
   dst[idx] = __builtin_bit_cast(unsigned short, h);
   if constexpr (SPLIT) dst[(size_t)total + idx] = __builtin_bit_cast(unsigned short, (__bf16)(w - (float)h));
 }
+template <bool SPLIT>
+__global__ void k_pack_frag_lp_multi(PackJobs J) {
+  pack_frag_lp_body<SPLIT>(J);
+}
+__global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF16>(J); }
 #include "catre_gram.h"
 #include "catre_small.h"
 #include "catre_train.h"
@@ -1575,6 +1582,8 @@ struct PackLayout {
   size_t bf_stn_c2, bf_stn_c3, bf_fstn_c1, bf_fstn_c2, bf_fstn_c3, bf_c2, bf_c3, bf_c4, bf_rot_l0[2], bf_rot_l1[2];
   // hi + lo bf16 fragment packs of the three split-mode layers (catre_split.h), offsets in floats
   size_t sp_stn_c2, sp_stn_c3, sp_fstn_c1, sp_fstn_c2, sp_fstn_c3, sp_c3, sp_c4, sp_rot_l0[2], sp_rot_l1[2];
+  // fp16 fragment packs of the bf16 packs' matrices, same layout (CATRE_PACK_F16, CATRE_DTYPE_F16), offsets in floats
+  size_t f16_stn_c2, f16_stn_c3, f16_fstn_c1, f16_fstn_c2, f16_fstn_c3, f16_c2, f16_c3, f16_c4, f16_rot_l0[2], f16_rot_l1[2];
 };
 
 PackLayout pack_layout(int ts_in) {
@@ -1620,6 +1629,18 @@ PackLayout pack_layout(int ts_in) {
   for (int h = 0; h < 2; ++h) {
     L.sp_rot_l0[h] = take(256 * 64);
     L.sp_rot_l1[h] = take(256 * 256);
+  }
+  L.f16_stn_c2 = take(128 * 64 / 2);
+  L.f16_stn_c3 = take(1024 * 128 / 2);
+  L.f16_fstn_c1 = take(64 * 64 / 2);
+  L.f16_fstn_c2 = take(128 * 64 / 2);
+  L.f16_fstn_c3 = take(1024 * 128 / 2);
+  L.f16_c2 = take(128 * 64 / 2);
+  L.f16_c3 = take(512 * 128 / 2);
+  L.f16_c4 = take(1024 * 512 / 2);
+  for (int h = 0; h < 2; ++h) {
+    L.f16_rot_l0[h] = take(256 * 64 / 2);
+    L.f16_rot_l1[h] = take(256 * 256 / 2);
   }
   // everything above is independent of ts_in (the stage entry points rely on that)
   L.ts_w0t = take((size_t)ts_in * 256);
@@ -1955,7 +1976,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
   hipStream_t st = (hipStream_t)stream;
   // a NULL source is skipped, so a sub-module (e.g. PointNetfeat alone) can pack just its own layers
   const bool enc32 = sel & CATRE_PACK_F32_ENCODER, head32 = sel & CATRE_PACK_F32_HEADS, bf = sel & CATRE_PACK_BF16,
-             sp = sel & CATRE_PACK_SPLIT, tails = sel & CATRE_PACK_F32_TAILS;
+             sp = sel & CATRE_PACK_SPLIT, tails = sel & CATRE_PACK_F32_TAILS, hf = sel & CATRE_PACK_F16;
   PackJobs jobs;
   jobs.n = 0;
   auto flush = [&]() {
@@ -1973,21 +1994,24 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     jobs.K[j] = K;
     jobs.end[j] = (j ? jobs.end[j - 1] : 0) + rows * K;
   };
-  PackJobs lpjobs;   // the bf16 / split packs: queued like the fp32 ones, one launch per kind
+  PackJobs lpjobs;   // the bf16 / split / fp16 packs: queued like the fp32 ones, one launch per kind
   lpjobs.n = 0;
-  auto flush_lp = [&](bool split_kind) {
+  enum { LP_BF16, LP_SPLIT, LP_F16 };
+  auto flush_lp = [&](int kind) {
     if (lpjobs.n) {
       const dim3 grid((lpjobs.end[lpjobs.n - 1] + 255) / 256);
-      if (split_kind)
+      if (kind == LP_SPLIT)
         hipLaunchKernelGGL(k_pack_frag_lp_multi<true>, grid, dim3(256), 0, st, lpjobs);
+      else if (kind == LP_F16)
+        hipLaunchKernelGGL(k_pack_frag_hf_multi, grid, dim3(256), 0, st, lpjobs);
       else
         hipLaunchKernelGGL(k_pack_frag_lp_multi<false>, grid, dim3(256), 0, st, lpjobs);
     }
     lpjobs.n = 0;
   };
-  auto frag_lp = [&](bool split_kind, const float* src, int ld, int coloff, int rows, int K, size_t off) {
+  auto frag_lp = [&](int kind, const float* src, int ld, int coloff, int rows, int K, size_t off) {
     if (!src) return;
-    if (lpjobs.n == PACK_MAX_JOBS) flush_lp(split_kind);
+    if (lpjobs.n == PACK_MAX_JOBS) flush_lp(kind);
     const int j = lpjobs.n++;
     lpjobs.src[j] = src;
     lpjobs.dst[j] = packed + off;
@@ -1997,7 +2021,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     lpjobs.end[j] = (j ? lpjobs.end[j - 1] : 0) + rows * K;
   };
   auto frag_bf = [&](const float* src, int ld, int coloff, int rows, int K, size_t off) {
-    frag_lp(false, src, ld, coloff, rows, K, off);
+    frag_lp(LP_BF16, src, ld, coloff, rows, K, off);
   };
   if (bf) {
   frag_bf(prm[CATRE_P_STN_CONV2_W], 64, 0, 128, 64, L.bf_stn_c2);
@@ -2013,10 +2037,29 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     frag_bf(prm[base], PMW, 1024, 256, 64, L.bf_rot_l0[h]);
     frag_bf(prm[base + 4], 256, 0, 256, 256, L.bf_rot_l1[h]);
   }
-  flush_lp(false);
+  flush_lp(LP_BF16);
+  }
+  if (hf) {  // the same matrices as the bf16 packs, as fp16
+    auto frag_hf = [&](const float* src, int ld, int coloff, int rows, int K, size_t off) {
+      frag_lp(LP_F16, src, ld, coloff, rows, K, off);
+    };
+    frag_hf(prm[CATRE_P_STN_CONV2_W], 64, 0, 128, 64, L.f16_stn_c2);
+    frag_hf(prm[CATRE_P_STN_CONV3_W], 128, 0, 1024, 128, L.f16_stn_c3);
+    frag_hf(prm[CATRE_P_FSTN_CONV1_W], 64, 0, 64, 64, L.f16_fstn_c1);
+    frag_hf(prm[CATRE_P_FSTN_CONV2_W], 64, 0, 128, 64, L.f16_fstn_c2);
+    frag_hf(prm[CATRE_P_FSTN_CONV3_W], 128, 0, 1024, 128, L.f16_fstn_c3);
+    frag_hf(prm[CATRE_P_CONV2_W], 64, 0, 128, 64, L.f16_c2);
+    frag_hf(prm[CATRE_P_CONV3_W], 128, 0, 512, 128, L.f16_c3);
+    frag_hf(prm[CATRE_P_CONV4_W], 512, 0, 1024, 512, L.f16_c4);
+    for (int h = 0; h < 2; ++h) {
+      const int base = h ? CATRE_P_ROTY_L0_W : CATRE_P_ROTX_L0_W;
+      frag_hf(prm[base], PMW, 1024, 256, 64, L.f16_rot_l0[h]);
+      frag_hf(prm[base + 4], 256, 0, 256, 256, L.f16_rot_l1[h]);
+    }
+    flush_lp(LP_F16);
   }
   auto frag_sp = [&](const float* src, int ld, int rows, int K, size_t off, int coloff = 0) {
-    frag_lp(true, src, ld, coloff, rows, K, off);
+    frag_lp(LP_SPLIT, src, ld, coloff, rows, K, off);
   };
   if (sp) {
   frag_sp(prm[CATRE_P_STN_CONV2_W], 64, 128, 64, L.sp_stn_c2);
@@ -2030,7 +2073,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
   frag_sp(prm[CATRE_P_ROTY_L0_W], PMW, 256, 64, L.sp_rot_l0[1], 1024);
   frag_sp(prm[CATRE_P_ROTX_L0_W + 4], 256, 256, 256, L.sp_rot_l1[0]);
   frag_sp(prm[CATRE_P_ROTY_L0_W + 4], 256, 256, 256, L.sp_rot_l1[1]);
-  flush_lp(true);
+  flush_lp(LP_SPLIT);
   }
   if (enc32) {
   frag(prm[CATRE_P_STN_CONV2_W], 64, 0, 128, 64, L.stn_c2);
@@ -2263,11 +2306,24 @@ int catre_pose_update(const float* rot6d, const float* trans_deltas, const float
 
 // One refine iteration on the bf16-operand kernels (catre_bf16.h); same launch chain, same workspace (pointfeat and
 // y1 hold bf16 in their fp32-sized slots), fp32 FC tails / ts head / pose update shared with the fp32 path.
+// OT = OpF16 (CATRE_DTYPE_F16): the same chain on the fp16-operand forms of the five kernels and the CATRE_PACK_F16 packs.
+// LP_LAUNCH(bf16 kernel, fp16 kernel, launch arguments...)
+#define LP_LAUNCH(KBF, KHF, ...)                 \
+  do {                                           \
+    if constexpr (is_f16_op<OT>())               \
+      hipLaunchKernelGGL(KHF, __VA_ARGS__);      \
+    else                                         \
+      hipLaunchKernelGGL(KBF, __VA_ARGS__);      \
+  } while (0)
+extern "C++" {  // (a template inside the C-ABI block)
+template <class OT>
 static int refine_iter_bf(const catre_points* pts, const float* init_pose, const float* init_scale,
                           const float* mean_scales, const float* Ks, const float* const* prm, const float* packed,
                           const catre_opts* o, float* pose_out, float* scale_out, float* ws, const WsLayout& W, int B,
                           int N, int M, hipStream_t st, float* pose_echo, float* scale_echo) {
   const PackLayout L = pack_layout(1);
+  // the operand pack of a layer: its bf16 or its fp16 image
+  auto pk = [&](size_t bf, size_t hf) { return pkb(packed, is_f16_op<OT>() ? hf : bf); };
   const int TN = (N + TP - 1) / TP, TM = (M + TP - 1) / TP, T = TN + TM, tiles = B * T;
   const int rd = catre_rot_dim(o->rot_type) / 2;
   int rc;
@@ -2278,13 +2334,13 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
   {
     ProfScope ps(CATRE_K_STN3D, st);
     if (paired)
-      hipLaunchKernelGGL(k_stn3d_bf2<false>, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                         prm[CATRE_P_STN_CONV1_B], pkb(packed, L.bf_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                         pkb(packed, L.bf_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
+      LP_LAUNCH((k_stn3d_bf2<false>), k_stn3d_hf2, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
+                prm[CATRE_P_STN_CONV1_B], pk(L.bf_stn_c2, L.f16_stn_c2), prm[CATRE_P_STN_CONV2_B],
+                pk(L.bf_stn_c3, L.f16_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
     else
-      hipLaunchKernelGGL((k_stn3d_bf<false>), dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                         prm[CATRE_P_STN_CONV1_B], pkb(packed, L.bf_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                         pkb(packed, L.bf_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
+      LP_LAUNCH((k_stn3d_bf<false>), k_stn3d_hf, dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
+                prm[CATRE_P_STN_CONV1_B], pk(L.bf_stn_c2, L.f16_stn_c2), prm[CATRE_P_STN_CONV2_B],
+                pk(L.bf_stn_c3, L.f16_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
   }
   hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.pool, 1024, 1024, B, N, M);
   if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_STN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans3, 3, 2 * B, st)))
@@ -2294,15 +2350,15 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
     {
       ProfScope ps(CATRE_K_STNKD, st);
       if (paired)
-        hipLaunchKernelGGL(k_stnkd_bf2<false>, dim3(pairs), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
-                           prm[CATRE_P_CONV1_B], pkb(packed, L.bf_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
-                           pkb(packed, L.bf_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.bf_fstn_c3),
-                           prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
+        LP_LAUNCH((k_stnkd_bf2<false>), k_stnkd_hf2, dim3(pairs), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
+                  prm[CATRE_P_CONV1_B], pk(L.bf_fstn_c1, L.f16_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
+                  pk(L.bf_fstn_c2, L.f16_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pk(L.bf_fstn_c3, L.f16_fstn_c3),
+                  prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
       else
-        hipLaunchKernelGGL((k_stnkd_bf<false>), dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
-                           prm[CATRE_P_CONV1_B], pkb(packed, L.bf_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
-                           pkb(packed, L.bf_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.bf_fstn_c3),
-                           prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
+        LP_LAUNCH((k_stnkd_bf<false>), k_stnkd_hf, dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
+                  prm[CATRE_P_CONV1_B], pk(L.bf_fstn_c1, L.f16_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
+                  pk(L.bf_fstn_c2, L.f16_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pk(L.bf_fstn_c3, L.f16_fstn_c3),
+                  prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
     }
     hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.pool, 1024, 1024, B, N, M);
     if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_FSTN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans64, 64, 2 * B, st)))
@@ -2313,15 +2369,15 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
   {
     ProfScope ps(CATRE_K_TRUNK, st);
     if (paired)
-      hipLaunchKernelGGL((k_trunk_bf2<false>), dim3(pairs), dim3(512), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
-                         prm[CATRE_P_CONV1_B], pkb(packed, L.bf_c2), prm[CATRE_P_CONV2_B], pkb(packed, L.bf_c3),
-                         prm[CATRE_P_CONV3_B], pkb(packed, L.bf_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                         g_trunk_trace);
+      LP_LAUNCH((k_trunk_bf2<false>), k_trunk_hf2, dim3(pairs), dim3(512), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
+                prm[CATRE_P_CONV1_B], pk(L.bf_c2, L.f16_c2), prm[CATRE_P_CONV2_B], pk(L.bf_c3, L.f16_c3),
+                prm[CATRE_P_CONV3_B], pk(L.bf_c4, L.f16_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
+                g_trunk_trace);
     else
-      hipLaunchKernelGGL(k_trunk_bf, dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
-                         prm[CATRE_P_CONV1_B], pkb(packed, L.bf_c2), prm[CATRE_P_CONV2_B], pkb(packed, L.bf_c3),
-                         prm[CATRE_P_CONV3_B], pkb(packed, L.bf_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                         g_trunk_trace);
+      LP_LAUNCH(k_trunk_bf, k_trunk_hf, dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
+                prm[CATRE_P_CONV1_B], pk(L.bf_c2, L.f16_c2), prm[CATRE_P_CONV2_B], pk(L.bf_c3, L.f16_c3),
+                prm[CATRE_P_CONV3_B], pk(L.bf_c4, L.f16_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
+                g_trunk_trace);
   }
   hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.gfeat, PMW, PMW, B, N, M);
   if ((rc = catre_ts_head(ws + W.gfeat, init_pose, init_scale, prm, packed, o, ws + W.dt, ws + W.ds, ws,
@@ -2340,8 +2396,8 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
     float* s1c = Gc + (size_t)2 * B * PF_NG * 4096;
     float* shc = s1c + (size_t)2 * B * PF_NG * 64;
     ProfScope ps(CATRE_K_ROT_L0_STATS, st);
-    hipLaunchKernelGGL(k_pf_moments_bf, dim3(2 * B, pf_groups(B)), dim3(256), 0, st, pointfeat, Gc, s1c,
-                       shc, B, N, M);
+    LP_LAUNCH(k_pf_moments_bf, k_pf_moments_hf, dim3(2 * B, pf_groups(B)), dim3(256), 0, st, pointfeat, Gc, s1c,
+              shc, B, N, M);
     hipLaunchKernelGGL(k_gn0_from_moments, dim3(B, gn0_shares(B)), dim3(256), 0, st, Gc, s1c, shc, prm[CATRE_P_ROTX_L0_W],
                        prm[CATRE_P_ROTY_L0_W], PMW, 1024, bias0, prm[CATRE_P_ROTX_GN0_W], prm[CATRE_P_ROTX_GN0_B],
                        prm[CATRE_P_ROTY_GN0_W], prm[CATRE_P_ROTY_GN0_B], ws + W.aff0, B, N, M);
@@ -2349,19 +2405,19 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
   unsigned short* y1 = reinterpret_cast<unsigned short*>(ws + W.y1);
   {
     ProfScope ps(CATRE_K_ROT_L1, st);
-    hipLaunchKernelGGL(k_rot_l1_bf, dim3(B * T), dim3(256), 0, st, pointfeat, pkb(packed, L.bf_rot_l0[0]),
-                       pkb(packed, L.bf_rot_l0[1]), ws + W.aff0, pkb(packed, L.bf_rot_l1[0]),
-                       pkb(packed, L.bf_rot_l1[1]), prm[CATRE_P_ROTX_L1_B], prm[CATRE_P_ROTY_L1_B], y1, ws + W.gn1, B,
-                       N, M, g_trunk_trace ? g_trunk_trace + ((size_t)1 << 24) : nullptr);
+    LP_LAUNCH(k_rot_l1_bf, k_rot_l1_hf, dim3(B * T), dim3(256), 0, st, pointfeat, pk(L.bf_rot_l0[0], L.f16_rot_l0[0]),
+              pk(L.bf_rot_l0[1], L.f16_rot_l0[1]), ws + W.aff0, pk(L.bf_rot_l1[0], L.f16_rot_l1[0]),
+              pk(L.bf_rot_l1[1], L.f16_rot_l1[1]), prm[CATRE_P_ROTX_L1_B], prm[CATRE_P_ROTY_L1_B], y1, ws + W.gn1, B,
+              N, M, g_trunk_trace ? g_trunk_trace + ((size_t)1 << 24) : nullptr);
   }
   hipLaunchKernelGGL(k_gn_finalize, dim3(B * 2), dim3(256), (size_t)T * 64 * sizeof(float), st, ws + W.gn1, ws + W.gn1stat,
                      N, M);
   {
     ProfScope ps(CATRE_K_ROT_OUT, st);
-    hipLaunchKernelGGL(k_rot_out_bf, dim3(B * T, 2), dim3(256), 0, st, y1, ws + W.gn1stat, prm[CATRE_P_ROTX_GN1_W],
-                       prm[CATRE_P_ROTX_GN1_B], prm[CATRE_P_ROTY_GN1_W], prm[CATRE_P_ROTY_GN1_B],
-                       prm[CATRE_P_ROTX_NECK_W], prm[CATRE_P_ROTY_NECK_W], prm[CATRE_P_ROTX_CONVP_W],
-                       prm[CATRE_P_ROTY_CONVP_W], ws + W.rpart, B, N, M, rd);
+    LP_LAUNCH(k_rot_out_bf, k_rot_out_hf, dim3(B * T, 2), dim3(256), 0, st, y1, ws + W.gn1stat, prm[CATRE_P_ROTX_GN1_W],
+              prm[CATRE_P_ROTX_GN1_B], prm[CATRE_P_ROTY_GN1_W], prm[CATRE_P_ROTY_GN1_B],
+              prm[CATRE_P_ROTX_NECK_W], prm[CATRE_P_ROTY_NECK_W], prm[CATRE_P_ROTX_CONVP_W],
+              prm[CATRE_P_ROTY_CONVP_W], ws + W.rpart, B, N, M, rd);
   }
   hipLaunchKernelGGL(k_rot_finish, dim3((B * 6 + 255) / 256), dim3(256), 0, st, ws + W.rpart, prm[CATRE_P_ROTX_NECK_B],
                      prm[CATRE_P_ROTY_NECK_B], packed + L.sumwp, prm[CATRE_P_ROTX_CONVP_B], prm[CATRE_P_ROTY_CONVP_B],
@@ -2370,6 +2426,8 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
   return pose_update_impl(ws + W.rot6d, ws + W.dt, ws + W.ds, init_pose, init_scale, mean_scales, Ks, o, pose_out,
                           scale_out, B, (void*)st, pose_echo, scale_echo);
 }
+}  // extern "C++"
+#undef LP_LAUNCH
 
 static int refine_iter_impl(const catre_points* pts, const float* init_pose, const float* init_scale,
                             const float* mean_scales, const float* Ks, const float* const* prm, const float* packed,
@@ -2385,8 +2443,11 @@ static int refine_iter_impl(const catre_points* pts, const float* init_pose, con
   // the two rot heads emit rot_dim values each: only even-width parametrisations can come out of them
   if (o->rot_type != CATRE_ROT_6D && o->rot_type != CATRE_ROT_QUAT) return CATRE_ERR_UNSUPPORTED;
   if (o->compute_dtype == CATRE_DTYPE_BF16)
-    return refine_iter_bf(pts, init_pose, init_scale, mean_scales, Ks, prm, packed, o, pose_out, scale_out, ws, W, B, N, M,
-                          st, pose_echo, scale_echo);
+    return refine_iter_bf<OpBf16>(pts, init_pose, init_scale, mean_scales, Ks, prm, packed, o, pose_out, scale_out, ws, W, B,
+                                  N, M, st, pose_echo, scale_echo);
+  if (o->compute_dtype == CATRE_DTYPE_F16)  // packed must hold CATRE_PACK_F16
+    return refine_iter_bf<OpF16>(pts, init_pose, init_scale, mean_scales, Ks, prm, packed, o, pose_out, scale_out, ws, W, B,
+                                 N, M, st, pose_echo, scale_echo);
   if (o->compute_dtype != CATRE_DTYPE_F32 && o->compute_dtype != CATRE_DTYPE_SPLIT) return CATRE_ERR_UNSUPPORTED;
   const bool split = o->compute_dtype == CATRE_DTYPE_SPLIT;
   const int T = (N + TP - 1) / TP + (M + TP - 1) / TP, R = 2 * B;

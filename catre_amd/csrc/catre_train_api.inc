@@ -295,6 +295,7 @@ int catre_op_gemm_rows_gn(const float* X, int ldx, const void* Wp, const float* 
   const CloudBias cb{per_cloud ? B : 0, N, M, gn_part};
   if (compute_dtype == CATRE_DTYPE_F32)
     return gemm_rows_f32_launch(X, ldx, nullptr, 0, (const float*)Wp, bias, nullptr, 0, Y, ldy, R, J, K, 0, stream, cb);
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(compute_dtype == CATRE_DTYPE_BF16 || compute_dtype == CATRE_DTYPE_SPLIT);
   return gemm_rows_bf_launch(X, ldx, nullptr, 0, Wp, bias, nullptr, 0, Y, ldy, R, J, K, 0, 0, (hipStream_t)stream,
                              compute_dtype == CATRE_DTYPE_SPLIT, cb);
@@ -417,6 +418,7 @@ int catre_op_gemm_tn_bias_lp(const float* dY, int ldy, const float* ymask, int l
 static int gemm_tn_impl(const float* dY, int ldy, const float* ymask, int ldym, const float* X, int ldx, float* dW,
                         float* db, int J, int K, int R, int accumulate, void* ws, size_t ws_bytes, int compute_dtype,
                         void* stream, const int* Rdev, const int* xrows, int x_bf16) {
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(compute_dtype == CATRE_DTYPE_F32 || compute_dtype == CATRE_DTYPE_BF16 || compute_dtype == CATRE_DTYPE_SPLIT);
   REQUIRE(!ymask || (ldym % 4) == 0);
   REQUIRE(dY && X && dW && ws && J > 0 && K > 0 && R > 0 && (ldy % 4) == 0 && (ldx % 4) == 0 && (J % 4) == 0 &&
@@ -489,6 +491,7 @@ static int gemm_tn_impl(const float* dY, int ldy, const float* ymask, int ldym, 
 // F32 and SPLIT: fp32 MFMAs.  Deterministic.
 int catre_op_fc_bwd(const float* dY, int ldy, const float* YM, const float* X, int ldx, const float* W, int ldw, float* dX,
                     float* dW, float* db, int R, int J, int Kx, int Kw, int compute_dtype, void* stream) {
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(compute_dtype == CATRE_DTYPE_F32 || compute_dtype == CATRE_DTYPE_BF16 || compute_dtype == CATRE_DTYPE_SPLIT);
   REQUIRE(dY && R > 0 && R < 2048 && J > 0 && Kx > 0 && Kw > 0 && ldy >= J && (dX || dW));
   REQUIRE(!dX || (W && ldw >= Kw));
@@ -786,6 +789,7 @@ int catre_op_gemm_rows_n(const float* X, int ldx, const float* xmask, int ldxm, 
   if (compute_dtype == CATRE_DTYPE_F32)
     return gemm_rows_f32_launch(X, ldx, xmask, ldxm, (const float*)Wp, bias, mask, ldm, Y, ldy, R, J, K, relu, stream,
                                 CloudBias{0, 0, 0, nullptr}, (const int*)nrows_dev);
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(compute_dtype == CATRE_DTYPE_BF16 || compute_dtype == CATRE_DTYPE_SPLIT);
   REQUIRE(X && Wp && Y && R > 0 && J > 0 && (ldx % 4) == 0 && (ldy % 4) == 0 && (J % 32) == 0);
   REQUIRE(J <= 1024 && (J <= 256 || J == 512 || J == 1024));
@@ -810,6 +814,7 @@ int catre_op_gemm_rows_nr(const float* X, int ldx, const float* xmask, int ldxm,
   REQUIRE(nrows_dev);
   const int mask_bf16 = (compute_dtype & CATRE_ROWS_BF16) != 0;  // `mask` holds bf16 rows (ldm in elements)
   compute_dtype &= ~CATRE_ROWS_BF16;
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(!mask_bf16 || (mask && compute_dtype == CATRE_DTYPE_BF16));
   if (compute_dtype == CATRE_DTYPE_F32)
     return gemm_rows_f32_launch(X, ldx, xmask, ldxm, (const float*)Wp, bias, mask, ldm, Y, ldy, R, J, K, relu, stream,
@@ -827,6 +832,7 @@ int catre_op_gemm_tn_bias_nr(const float* dY, int ldy, const float* ymask, int l
   REQUIRE(nrows_dev);
   const int x_bf16 = (compute_dtype & CATRE_ROWS_BF16) != 0;  // X holds bf16 rows (ldx in elements)
   compute_dtype &= ~CATRE_ROWS_BF16;
+  if (compute_dtype == CATRE_DTYPE_F16) return CATRE_ERR_UNSUPPORTED;  // fp16 operands: inference (catre_refine_*) only
   REQUIRE(!x_bf16 || (compute_dtype == CATRE_DTYPE_BF16 && !tn_skinny(J, K)));
   return gemm_tn_impl(dY, ldy, ymask, ldym, X, ldx, dW, db, J, K, R, accumulate, ws, ws_bytes, compute_dtype, stream,
                       (const int*)nrows_dev, (const int*)x_rows, x_bf16);

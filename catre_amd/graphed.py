@@ -212,6 +212,8 @@ class GraphedRefine:
         # the scratch buffer the captured kernels point at: owned here, whatever the runtime's per-stream cache does
         self._ws = rt._ws.get((dev.index, side.cuda_stream))
         self._packed = rt._packed
+        # the packs the captured chain reads (its compute mode is fixed at capture: the fp16 one reads packs outside PACK_ALL)
+        self._sel = rt._refine_packs(self.model._inference_opts())
         self._ptrs = self._param_ptrs()
         self._side = side
 
@@ -219,7 +221,7 @@ class GraphedRefine:
     def __call__(self, batch):
         rt = self.model._runtime()
         with torch.cuda.device(self.dev):
-            rt.params(self.dev)  # stale packed weights are re-packed in place, stream-ordered before the replay
+            rt.params(self.dev, self._sel)  # stale packed weights are re-packed in place, stream-ordered before the replay
             if rt._packed is not self._packed or self._param_ptrs() != self._ptrs:
                 self._capture(1)  # parameters moved: the captured pointers are stale
             self._stage(batch)

@@ -57,9 +57,10 @@ class CatreOpts(ctypes.Structure):
     ]
 
 
-DTYPE_F32, DTYPE_BF16, DTYPE_SPLIT = 0, 1, 2
+DTYPE_F32, DTYPE_BF16, DTYPE_SPLIT, DTYPE_F16 = 0, 1, 2, 3
 ROWS_BF16 = 0x100   # CATRE_ROWS_BF16
 PACK_F32_ENCODER, PACK_F32_HEADS, PACK_BF16, PACK_SPLIT, PACK_F32_TAILS, PACK_ALL = 1, 2, 4, 8, 16, 31
+PACK_F16 = 32       # CATRE_PACK_F16: the fp16 packs DTYPE_F16 reads (not part of PACK_ALL)
 ROT_6D, ROT_QUAT, ROT_LOG_QUAT, ROT_LIE_VEC = 0, 1, 2, 3
 ROT_DIMS = {ROT_6D: 6, ROT_QUAT: 4, ROT_LOG_QUAT: 3, ROT_LIE_VEC: 3}
 

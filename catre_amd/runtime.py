@@ -167,6 +167,12 @@ class HipRuntime:
         return ws
 
     # ------------------------------------------------------------------ drivers
+    @staticmethod
+    def _refine_packs(opts):
+        """The packs a fused refine in ``opts.compute_dtype`` reads: every pack of the fp32 / bf16 / split modes, and the
+        fp16 ones on top for DTYPE_F16 (``params`` repacks with the union when a cached image lacks some)."""
+        return hip.PACK_ALL | hip.PACK_F16 if opts.compute_dtype == hip.DTYPE_F16 else hip.PACK_ALL
+
     def refine_iter(self, x, tfd_kps, init_pose, init_scale, K_zoom, mean_scales, opts):
         """One ``CATRE_disR_shared.forward`` (test path) -> (pose [B,3,4], scale [B,3])."""
         lib = hip.load()
@@ -182,7 +188,7 @@ class HipRuntime:
             assert Ks is not None and Ks.shape == (B, 3, 3)  # pose_scale_from_delta_init.py:64
         if opts.scale_base_mean and ms is None:
             raise ValueError("SCLAE_TYPE without 'iter' needs mean_scales")
-        prm, packed = self.params(dev)
+        prm, packed = self.params(dev, self._refine_packs(opts))
         ws = self.workspace(B, N, M, dev)
         pose_out = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
         scale_out = torch.empty(B, 3, dtype=torch.float32, device=dev)
@@ -210,7 +216,7 @@ class HipRuntime:
             raise ValueError("T_TRANSFORM_K_AWARE needs K")
         if opts.scale_base_mean and ms is None:
             raise ValueError("SCLAE_TYPE without 'iter' needs mean_scales")
-        prm, packed = self.params(dev)
+        prm, packed = self.params(dev, self._refine_packs(opts))
         ws = self.workspace(B, N, M, dev)
         poses = torch.empty(n_iter + 1, B, 3, 4, dtype=torch.float32, device=dev)
         scales = torch.empty(n_iter + 1, B, 3, dtype=torch.float32, device=dev)

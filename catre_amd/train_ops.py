@@ -111,7 +111,7 @@ def autocast_on():
             logger.warning("torch.autocast asks for float16: catre_amd's reduced-precision kernels use BFLOAT16 operands "
                            "(fp32 accumulation / outputs) for any autocast dtype - 8-bit significands instead of 11.  "
                            "MODEL.CATRE.COMPUTE_DTYPE='split' keeps fp32-grade results on the bf16 matrix pipe, 'fp32' "
-                           "ignores autocast.")
+                           "ignores autocast; for inference, 'fp16' takes fp16 operands at the bf16 mode's rate.")
     return True
 
 

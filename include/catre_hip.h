@@ -96,7 +96,12 @@ typedef struct catre_opts {
   int32_t rot_input_is_matrix; /* catre_pose_update only: `rot6d` holds [B,3,3] matrices (get_rot_mat already applied) */
   int32_t compute_dtype;       /* catre_refine_iter / catre_refine_k: CATRE_DTYPE_F32 (default) or CATRE_DTYPE_BF16 -
                                 * what torch.cuda.amp.autocast selects in the reference (engine.py:304, TEST.AMP_TEST):
-                                * bf16 GEMM operands, fp32 accumulation / GroupNorm statistics / SO(3) update          */
+                                * bf16 GEMM operands, fp32 accumulation / GroupNorm statistics / SO(3) update;
+                                * CATRE_DTYPE_SPLIT; or CATRE_DTYPE_F16 - the bf16 path's structure with fp16 operands
+                                * (the dtype of the reference's autocast on "cuda").  F16 is inference only:
+                                * catre_refine_iter, catre_refine_k and catre_refine_k_from accept it, and their
+                                * `packed` image must have been made with CATRE_PACK_F16; every other entry point that
+                                * takes a compute_dtype returns CATRE_ERR_UNSUPPORTED for it                            */
   int32_t rot_type;            /* parametrisation of the rotation residual, the part of ROT_HEAD.ROT_TYPE after ego_/allo_
                                 * (get_rot_mat, core/catre/models/model_utils.py:28-40): CATRE_ROT_6D (default, [B,6]),
                                 * CATRE_ROT_QUAT ([B,4]), CATRE_ROT_LOG_QUAT ([B,3]), CATRE_ROT_LIE_VEC ([B,3]).  The fused
@@ -109,7 +114,7 @@ enum { CATRE_ROT_6D = 0, CATRE_ROT_QUAT = 1, CATRE_ROT_LOG_QUAT = 2, CATRE_ROT_L
 
 /* CATRE_DTYPE_SPLIT: fp32 results from split-bf16 (hi + lo, three products) MFMAs on the layers holding 98 % of the FLOPs;
  * same parity bound as CATRE_DTYPE_F32 */
-enum { CATRE_DTYPE_F32 = 0, CATRE_DTYPE_BF16 = 1, CATRE_DTYPE_SPLIT = 2 };
+enum { CATRE_DTYPE_F32 = 0, CATRE_DTYPE_BF16 = 1, CATRE_DTYPE_SPLIT = 2, CATRE_DTYPE_F16 = 3 };
 /* OR-ed into the compute_dtype of catre_op_gemm_rows_nr / catre_op_gemm_tn_bias_nr (with CATRE_DTYPE_BF16): the row-indexed
  * dense tensor - `mask` / `X` - holds bf16 rows (leading dimension in ELEMENTS): the activation rows the autocast encoder
  * forward saves (catre_train_*_fwd with CATRE_DTYPE_BF16) */
@@ -139,7 +144,8 @@ enum {
   CATRE_PACK_F32_TAILS = 16, /* with _F32_HEADS: the ts head's transposed weights and the conv_p weight sums - read by the
                                 inference tail kernels only, so a training forward (which re-packs every iteration) leaves
                                 these four launches out */
-  CATRE_PACK_ALL = 31
+  CATRE_PACK_ALL = 31,       /* every pack of the fp32 / bf16 / split modes */
+  CATRE_PACK_F16 = 32        /* the fp16 fragments of the bf16 packs' matrices (CATRE_DTYPE_F16; not part of _ALL) */
 };
 int catre_pack_weights_sel(const float* const* params, int N, int M, int ts_in_dim, float* packed, size_t packed_floats,
                            int sel, void* stream);
