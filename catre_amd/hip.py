@@ -79,6 +79,19 @@ class CatreLossCfg(ctypes.Structure):
                [(n, ctypes.c_float) for n in ("pm_lw", "rot_lw", "trans_lw", "scale_lw")]
 
 
+class CatreLossCfg2(ctypes.Structure):
+    """catre_loss_cfg2: the fields of catre_loss_cfg (reached by their own names) + the point-matching form."""
+    _anonymous_ = ("base",)
+    _fields_ = [("base", CatreLossCfg), ("pm_mode", ctypes.c_int32), ("pm_elem", ctypes.c_int32),
+                ("pm_use_bbox", ctypes.c_int32), ("pm_beta", ctypes.c_float)]
+
+
+# CATRE_PM_* / CATRE_PM_ELEM_* of include/catre_hip.h
+PM_R_ONLY, PM_RT, PM_R_T_POINTS, PM_R_T_DIRECT, PM_R_XY_Z_POINTS, PM_R_XY_Z_DIRECT = range(6)
+PM_ELEM_L1, PM_ELEM_SMOOTH_L1, PM_ELEM_MSE, PM_ELEM_L2 = range(4)
+LOSS2_TERMS, LOSS2_PART = 8, 10
+
+
 class CatrePoints(ctypes.Structure):
     _fields_ = [
         ("obs", ctypes.c_void_p), ("obs_sb", ctypes.c_int64), ("obs_sn", ctypes.c_int64), ("obs_sc", ctypes.c_int64),
@@ -209,6 +222,8 @@ _SIGS = {
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),
     "catre_loss_bwd_sums": (_I, [_P] * 13 + [_I, _P, _P, _P, _I, _I, _I, _P]),
+    "catre_loss_fwd2": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),
+    "catre_loss_bwd2": (_I, [_P] * 13 + [_I, _P, _P, _P, _I, _I, _I, _P]),
     "catre_profile_enable": (_I, [_I, _I]),
     "catre_profile_collect": (_I, [_P, _I, _P]),
     "catre_debug_trunk_trace": (_I, [_P]),

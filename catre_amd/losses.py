@@ -1,13 +1,13 @@
 """Device-side training loss: the terms of ``CATRE_disR_shared.catre_loss``
-(reference ``core/catre/models/CATRE_disR_shared.py:168-288``) and ``PyPMLoss``
-(``core/catre/losses/pm_loss.py:85-194``) for the shipped loss configuration.
+(reference ``core/catre/models/CATRE_disR_shared.py:168-288``) and the whole of ``PyPMLoss``
+(``core/catre/losses/pm_loss.py:21-194``: six structural modes x four element losses x with-scale x symmetric x bbox).
 
 The reference picks the symmetry-equivalent ground-truth rotation per object in a Python/numpy loop on the
 host (``core/utils/pose_utils.py:472-528``: up to 314 ``re()`` evaluations per symmetric object and a
 device->host copy per refine iteration) and then evaluates the terms with ~100 small torch kernels.  Here the
-whole loss is two HIP launches forward (``catre_loss_fwd``: candidate arg-max, the point-matching sum and the
-per-object terms in one workgroup per object, then an ordered reduction) and one backward (``catre_loss_bwd``),
-chained into autograd by :class:`_FusedLoss`; no value ever leaves the device.
+whole loss is two HIP launches forward (``catre_loss_fwd2``: candidate arg-max, the point-matching sums and the
+per-object terms in one workgroup per object, then an ordered reduction) and one backward (``catre_loss_bwd2``),
+chained into autograd by :class:`_FusedLoss`; no value ever leaves the device.  Every form takes the same launches.
 """
 import ctypes
 
@@ -18,6 +18,33 @@ from . import hip
 
 _sym_cache = {}
 _KEYS = ("loss_PM_R", "loss_rot", "loss_yaxis_rot", "loss_trans_xy", "loss_trans_z", "loss_scale")
+N_LOSS = hip.LOSS2_TERMS   # loss slots of catre_loss_fwd2: the six above, then the second and the third PM term
+
+# structural modes of PyPMLoss in the order of CATRE_PM_* -> the dict keys of each, in the reference's insertion order
+# (pm_loss.py:126-192), with the loss slot that holds it
+PM_MODES = ("r_only", "rt", "r_t_points", "r_t_direct", "r_xy_z_points", "r_xy_z_direct")
+PM_KEYS = {
+    hip.PM_R_ONLY: (("loss_PM_R", 0),),
+    hip.PM_RT: (("loss_PM_RT", 0),),
+    hip.PM_R_T_POINTS: (("loss_PM_R", 0), ("loss_PM_T", 6)),
+    hip.PM_R_T_DIRECT: (("loss_PM_R", 0), ("loss_PM_T_noP", 6)),
+    hip.PM_R_XY_Z_POINTS: (("loss_PM_R", 0), ("loss_PM_xy", 6), ("loss_PM_z", 7)),
+    hip.PM_R_XY_Z_DIRECT: (("loss_PM_R", 0), ("loss_PM_xy_noP", 6), ("loss_PM_z_noP", 7)),
+}
+_PM_ELEMS = {"l1": hip.PM_ELEM_L1, "smooth_l1": hip.PM_ELEM_SMOOTH_L1, "mse": hip.PM_ELEM_MSE, "l2": hip.PM_ELEM_L2}
+
+
+def pm_mode(lc):
+    """LOSS_CFG -> CATRE_PM_*, as PyPMLoss resolves its switches (pm_loss.py:56-68 and the branch order of :126-191):
+    r_only first; disentangle_z forces disentangle_t; without any disentangling t_loss_use_points is forced on."""
+    if lc.PM_R_ONLY:
+        return hip.PM_R_ONLY
+    use_points = bool(lc.get("PM_T_USE_POINTS", False))
+    if lc.get("PM_DISENTANGLE_Z", False):
+        return hip.PM_R_XY_Z_POINTS if use_points else hip.PM_R_XY_Z_DIRECT
+    if lc.get("PM_DISENTANGLE_T", False):
+        return hip.PM_R_T_POINTS if use_points else hip.PM_R_T_DIRECT
+    return hip.PM_RT
 
 
 def _sym_tensor(sym_infos, device, dtype):
@@ -54,10 +81,15 @@ _NORM_TYPES = {"L1": 0, "MSE": 1, "L2": 2}
 
 def _loss_cfg_struct(cfg):
     lc = cfg.MODEL.CATRE.LOSS_CFG
-    c = hip.CatreLossCfg()
+    c = hip.CatreLossCfg2()
     c.pm_on = int(lc.PM_LW > 0)
-    if c.pm_on and (lc.PM_LOSS_TYPE.lower() != "l1" or not lc.PM_R_ONLY or lc.get("PM_USE_BBOX", False)):
-        raise NotImplementedError("PM loss: the shipped configuration (L1, R-only) is implemented")
+    c.pm_beta = 1.0
+    if c.pm_on:
+        loss_type = lc.PM_LOSS_TYPE.lower()
+        if loss_type not in _PM_ELEMS:
+            raise ValueError("loss type {} not supported.".format(loss_type))  # pm_loss.py:82
+        c.pm_mode, c.pm_elem, c.pm_use_bbox = pm_mode(lc), _PM_ELEMS[loss_type], int(bool(lc.get("PM_USE_BBOX", False)))
+        c.pm_beta = float(lc.get("PM_SMOOTH_L1_BETA", 1.0))
     c.pm_sym, c.pm_with_scale = int(bool(lc.PM_LOSS_SYM)), int(bool(lc.PM_WITH_SCALE))
     c.rot_on = int(lc.ROT_LW > 0)
     if c.rot_on:
@@ -81,33 +113,36 @@ def _loss_cfg_struct(cfg):
 
 
 class _FusedLoss(torch.autograd.Function):
-    """-> (losses [6], vis [N_VIS], prefix [len(terms)]): the six loss terms, the logging scalars, and the running sums
+    """-> (losses [N_LOSS], vis [N_VIS], prefix [len(terms)]): the loss slots, the logging scalars, and the running sums
     ((0 + l[t0]) + l[t1]) + ... of the terms the loss dict will hold, in its order (see :class:`_LossTerm`)."""
 
     @staticmethod
     def forward(ctx, pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, valid, is_sym, lcfg, trans_deltas, terms):
         lib = hip.load()
-        B, M, S1 = pose.shape[0], (kps.shape[1] if kps is not None else 0), cands.shape[1]
+        # PM_USE_BBOX: the eight cube corners are generated in the kernel, obj_kps is not read (pm_loss.py:114-117)
+        B, M, S1 = pose.shape[0], (8 if lcfg.pm_use_bbox else kps.shape[1] if kps is not None else 0), cands.shape[1]
+        if lcfg.pm_use_bbox:
+            kps = None
         dev = pose.device
         best = torch.empty(B, dtype=torch.int32, device=dev)
         counts = torch.empty(2, dtype=torch.int32, device=dev)
-        part = torch.empty(B * 8, dtype=torch.float32, device=dev)
+        part = torch.empty(B * hip.LOSS2_PART, dtype=torch.float32, device=dev)
         n = len(terms)
-        buf = torch.empty(6 + N_VIS + n, dtype=torch.float32, device=dev)
+        buf = torch.empty(N_LOSS + N_VIS + n, dtype=torch.float32, device=dev)
         tarr = (ctypes.c_int32 * max(n, 1))(*terms)
-        hip.check(lib.catre_loss_fwd_sums(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
-                                          hip.ptr(kps), hip.ptr(cands), hip.ptr(valid), hip.ptr(is_sym), ctypes.byref(lcfg),
-                                          hip.ptr(best), hip.ptr(counts), hip.ptr(part), hip.ptr(buf), hip.ptr(trans_deltas),
-                                          tarr, n, hip.ptr(buf[6 + N_VIS:]) if n else None, B, M, S1, hip.stream_ptr(dev)),
-                  "catre_loss_fwd_sums")
+        hip.check(lib.catre_loss_fwd2(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
+                                      hip.ptr(kps), hip.ptr(cands), hip.ptr(valid), hip.ptr(is_sym), ctypes.byref(lcfg),
+                                      hip.ptr(best), hip.ptr(counts), hip.ptr(part), hip.ptr(buf), hip.ptr(trans_deltas),
+                                      tarr, n, hip.ptr(buf[N_LOSS + N_VIS:]) if n else None, B, M, S1, hip.stream_ptr(dev)),
+                  "catre_loss_fwd2")
         ctx.save_for_backward(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts)
         ctx.lcfg, ctx.dims, ctx.terms = lcfg, (B, M, S1), tuple(terms)
         ctx.set_materialize_grads(False)
-        losses, vis = buf[:6], buf[6:6 + N_VIS]
+        losses, vis = buf[:N_LOSS], buf[N_LOSS:N_LOSS + N_VIS]
         ctx.mark_non_differentiable(vis)
         # the running sums as separate 0-dim outputs: the gradient of the one that gets used arrives alone (an unbind of
         # one vector would zero-fill the other five and stack them)
-        return (losses, vis) + tuple(buf[6 + N_VIS + k] for k in range(n))
+        return (losses, vis) + tuple(buf[N_LOSS + N_VIS + k] for k in range(n))
 
     @staticmethod
     def backward(ctx, up, _up_vis, *up_sums):
@@ -122,11 +157,11 @@ class _FusedLoss(torch.autograd.Function):
         ups = [u.reshape(1).float().contiguous() if u is not None else None for u in up_sums]   # (no-ops for fp32 scalars)
         parr = (ctypes.c_void_p * max(n, 1))(*[u.data_ptr() if u is not None else None for u in ups])
         dpose, dscale = torch.empty_like(pose), torch.empty_like(scale)
-        hip.check(lib.catre_loss_bwd_sums(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
-                                          hip.ptr(kps), hip.ptr(cands), hip.ptr(is_sym), hip.ptr(best), hip.ptr(counts),
-                                          hip.ptr(up), parr if any(u is not None for u in ups) else None, tarr, n,
-                                          ctypes.byref(ctx.lcfg), hip.ptr(dpose), hip.ptr(dscale), B, M, S1,
-                                          hip.stream_ptr(pose.device)), "catre_loss_bwd_sums")
+        hip.check(lib.catre_loss_bwd2(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
+                                      hip.ptr(kps), hip.ptr(cands), hip.ptr(is_sym), hip.ptr(best), hip.ptr(counts),
+                                      hip.ptr(up), parr if any(u is not None for u in ups) else None, tarr, n,
+                                      ctypes.byref(ctx.lcfg), hip.ptr(dpose), hip.ptr(dscale), B, M, S1,
+                                      hip.stream_ptr(pose.device)), "catre_loss_bwd2")
         return (dpose, dscale) + (None,) * 10
 
 
@@ -262,7 +297,7 @@ def catre_loss(cfg, out_rot, out_trans, out_scale, gt_rot, gt_trans, gt_scale, o
     # the dict's keys -> loss indices, in the reference's insertion order (CATRE_disR_shared.py:168-288)
     keys = []
     if lcfg.pm_on:
-        keys.append(("loss_PM_R", 0))
+        keys += PM_KEYS[lcfg.pm_mode]
     if lcfg.rot_on:
         if n_nonsym > 0:
             keys.append(("loss_rot", 1))
@@ -274,7 +309,7 @@ def catre_loss(cfg, out_rot, out_trans, out_scale, gt_rot, gt_trans, gt_scale, o
         keys.append(("loss_scale", 5))
     losses, vis, *prefix = _FusedLoss.apply(hip.require_dev_f32(pose, "pose"), f32(out_scale), f32(gt_rot), f32(gt_trans), gs,
                                            f32(obj_kps), cands, valid, is_sym, lcfg, td, [i for _, i in keys])
-    losses = losses.unbind(0)  # six 0-dim views; their backward is one stack instead of six zero-fill + index + add chains
+    losses = losses.unbind(0)  # 0-dim views; their backward is one stack instead of six zero-fill + index + add chains
     tok = object()
     sums = [t.as_subclass(_LossTerm) for t in prefix]
     for k, t in enumerate(sums):

@@ -700,7 +700,8 @@ int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, si
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
- * (core/catre/models/CATRE_disR_shared.py:168-288; PyPMLoss core/catre/losses/pm_loss.py:85-194, L1 / R-only form). */
+ * (core/catre/models/CATRE_disR_shared.py:168-288; PyPMLoss core/catre/losses/pm_loss.py:85-194, L1 / R-only form -
+ * catre_loss_cfg2 below selects the other forms). */
 typedef struct catre_loss_cfg {
   int32_t pm_on, pm_sym, pm_with_scale;     /* PM_LW > 0, PM_LOSS_SYM, PM_WITH_SCALE                              */
   int32_t rot_on, rot_l2, yaxis_smooth;     /* ROT_LW > 0, ROT_LOSS_TYPE == "L2" (else angular), ROT_YAXIS_LOSS_TYPE: 0 "L1",
@@ -748,6 +749,66 @@ int catre_loss_bwd_sums(const float* pose, const float* scale, const float* gt_r
                         const int32_t* best, const int32_t* counts, const float* upstream,
                         const float* const* up_prefix, const int32_t* terms, int n_terms, const catre_loss_cfg* cfg,
                         float* dpose, float* dscale, int B, int M, int S1, void* stream);
+
+/* ---- every form of the point-matching loss (PyPMLoss, core/catre/losses/pm_loss.py:21-194) -------------------------
+ * The four entry points above keep their layout, meaning and result bits (L1 / R-only point-matching term).  The *2
+ * entry points below run the same three kernels for every form CATRE_disR_shared.catre_loss can select
+ * (core/catre/models/CATRE_disR_shared.py:185-210). */
+
+/* Structural mode, as PyPMLoss.__init__ resolves its switches (pm_loss.py:56-68: disentangle_z forces disentangle_t;
+ * without any disentangling t_loss_use_points is forced on), and the dict keys of each (pm_loss.py:126-192). */
+enum {
+  CATRE_PM_R_ONLY = 0,        /* PM_R_ONLY (pm_loss.py:126-128):                                  loss_PM_R                */
+  CATRE_PM_RT = 1,            /* none of the switches (:187-191):                                 loss_PM_RT               */
+  CATRE_PM_R_T_POINTS = 2,    /* PM_DISENTANGLE_T, PM_T_USE_POINTS (:168-178):                    loss_PM_R, loss_PM_T     */
+  CATRE_PM_R_T_DIRECT = 3,    /* PM_DISENTANGLE_T (:179-185):                                     loss_PM_R, loss_PM_T_noP */
+  CATRE_PM_R_XY_Z_POINTS = 4, /* PM_DISENTANGLE_Z, PM_T_USE_POINTS (:132-156):      loss_PM_R, loss_PM_xy, loss_PM_z       */
+  CATRE_PM_R_XY_Z_DIRECT = 5, /* PM_DISENTANGLE_Z (:157-165):               loss_PM_R, loss_PM_xy_noP, loss_PM_z_noP       */
+  CATRE_PM_MODE_COUNT = 6
+};
+/* Element loss, PM_LOSS_TYPE.lower() (pm_loss.py:70-82). */
+enum {
+  CATRE_PM_ELEM_L1 = 0,        /* "l1": nn.L1Loss                                                                          */
+  CATRE_PM_ELEM_SMOOTH_L1 = 1, /* "smooth_l1": fvcore.nn.smooth_l1_loss with PM_SMOOTH_L1_BETA (below 1e-5: L1)             */
+  CATRE_PM_ELEM_MSE = 2,       /* "mse": nn.MSELoss                                                                        */
+  CATRE_PM_ELEM_L2 = 3,        /* "l2": L2Loss (core/catre/losses/l2_loss.py:5-28): one norm per object over all of its
+                                * differences, mean over objects                                                           */
+  CATRE_PM_ELEM_COUNT = 4
+};
+#define CATRE_LOSS2_TERMS 8 /* loss slots of the *2 entry points (a loss dict holds at most eight terms)                   */
+#define CATRE_LOSS2_PART 10 /* floats of part_ws per object                                                                */
+
+typedef struct catre_loss_cfg2 {
+  catre_loss_cfg base; /* every field above, unchanged (CATRE_disR_shared.py:168-288)                                      */
+  int32_t pm_mode;     /* CATRE_PM_*: PM_R_ONLY / PM_DISENTANGLE_T / PM_DISENTANGLE_Z / PM_T_USE_POINTS (pm_loss.py:56-68) */
+  int32_t pm_elem;     /* CATRE_PM_ELEM_*: PM_LOSS_TYPE (pm_loss.py:70-82)                                                 */
+  int32_t pm_use_bbox; /* PM_USE_BBOX (pm_loss.py:114-117): the points are the eight corners of the unit cube in the order
+                        * of get_normed_bbox (core/catre/engine/engine_utils.py:66-80), generated in the kernel: kps is not
+                        * read and M must be 8                                                                             */
+  float pm_beta;       /* PM_SMOOTH_L1_BETA (CATRE_disR_shared.py:189; read by CATRE_PM_ELEM_SMOOTH_L1 only)               */
+} catre_loss_cfg2;
+
+/* losses[22]: [0..8) = the six terms of catre_loss_fwd, where slot 0 is the first PM term (loss_PM_R, or loss_PM_RT in
+ * CATRE_PM_RT), then 6 = the second PM term (loss_PM_T / loss_PM_T_noP / loss_PM_xy / loss_PM_xy_noP) and 7 = the third
+ * (loss_PM_z / loss_PM_z_noP); a slot the mode does not have is 0.  [8..22) = the 14 logging scalars of catre_loss_fwd.
+ * The point terms carry 3 * PM_LW, the `_noP` terms neither (pm_loss.py:160-164,181-184).  part_ws: B * CATRE_LOSS2_PART
+ * floats.  terms / prefix as in catre_loss_fwd_sums with n_terms <= 8 and indices < 8 (both may be NULL / 0).
+ * An unknown pm_mode / pm_elem returns CATRE_ERR_BAD_ARG before anything is launched.  With pm_mode ==
+ * CATRE_PM_R_ONLY, CATRE_PM_ELEM_L1 and no bbox, slots 0..5, the scalars, dpose and dscale carry the bits of the
+ * first entry points. */
+int catre_loss_fwd2(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const unsigned char* valid,
+                    const int32_t* is_sym, const catre_loss_cfg2* cfg, int32_t* best, int32_t* counts, float* part_ws,
+                    float* losses, const float* trans_deltas, const int32_t* terms, int n_terms, float* prefix, int B,
+                    int M, int S1, void* stream);
+/* dpose [B,3,4], dscale [B,3] = gradient of sum_i upstream[i] * losses[i] (upstream: 8 floats on the device, may be NULL)
+ * plus the prefix sums' upstreams as in catre_loss_bwd_sums (up_prefix: HOST array of n_terms device pointers).  The PM
+ * terms' gradient reaches the translation column of dpose in every mode but CATRE_PM_R_ONLY. */
+int catre_loss_bwd2(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const int32_t* is_sym,
+                    const int32_t* best, const int32_t* counts, const float* upstream, const float* const* up_prefix,
+                    const int32_t* terms, int n_terms, const catre_loss_cfg2* cfg, float* dpose, float* dscale, int B,
+                    int M, int S1, void* stream);
 
 #ifdef __cplusplus
 }
