@@ -810,6 +810,61 @@ int catre_loss_bwd2(const float* pose, const float* scale, const float* gt_rot, 
                     const int32_t* terms, int n_terms, const catre_loss_cfg2* cfg, float* dpose, float* dscale, int B,
                     int M, int S1, void* stream);
 
+/* ---- evaluation of refined poses: 3D IoU, degree / cm, greedy matching (core/catre/engine/test_utils.py:523-757) ------
+ * What compute_independent_mAP (test_utils.py:760-924) does per image and class, for every image, class, evaluated refine
+ * iteration and threshold in three launches.  The per-class AP integration (:112-137) and every ordering by score stay on
+ * the host (catre_amd/evaluation.py): the device receives permutations.
+ *
+ * A GROUP is one (image, class) pair.  Group g holds the predictions pred_off[g] .. pred_off[g+1] (in the order the
+ * reference matches them: np.argsort(scores)[::-1] of the group, :557) and the GTs gt_off[g] .. gt_off[g+1]; its np x ng
+ * pairs start at pair_off[g], prediction-major.  pred_off / gt_off / pair_off: G + 1 int32 each, non-decreasing, ending at
+ * P / NG / Q.  pair_group [Q]: the group of each pair.  pred_idx [P]: the row (< N) of each prediction in pred_pose
+ * [T, N, 3, 4] / pred_scale [T, N, 3], T = evaluated iterations (GTs are shared by all of them).  gt_pose [NG, 3, 4],
+ * gt_scale [NG, 3], gt_hv [NG] = mug handle visibility.  All poses and scales are float32 as the model returns them and
+ * are widened to double; every result below is computed in double. */
+enum {
+  CATRE_EVAL_GENERIC = 0, /* trace formula with the clip (:681-683), plain IoU                                            */
+  CATRE_EVAL_YSYM = 1,    /* bottle / bowl / can: y-axis angle (:665-669), IoU maximised over 20 y rotations of the
+                           * PREDICTION (:178-201)                                                                         */
+  CATRE_EVAL_MUG = 2,     /* mug: as YSYM for a GT with handle visibility 0 (:179, :671), as GENERIC otherwise             */
+  CATRE_EVAL_FLIP = 3,    /* phone / eggbox / glue: min over a 180 degree y flip (:676-680), plain IoU                     */
+  CATRE_EVAL_MODE_COUNT = 4
+};
+#define CATRE_EVAL_NROT 20 /* y rotations of a symmetric prediction (:197) */
+
+/* iou [T, Q] float32 (the reference stores it in a float32 array, :567, and compares that) and degcm [T, Q, 2] double =
+ * (degree, cm) of every pair (compute_3d_iou_new :140-205, compute_RT_degree_cm_symmetry :619-689; both rotation blocks
+ * divided by cbrt(det), cm = 100 |t1 - t2|).  group_mode [G]: CATRE_EVAL_* of the group's class.  cos_sin: device
+ * array of CATRE_EVAL_NROT (cos, sin) double pairs of 2 pi i / 20, computed by the caller with the reference's own
+ * numpy calls (:187-200) so that they are its bits.  Deviation: the arccos argument is clamped to [-1, 1] in every
+ * branch (the reference clamps the generic one only and returns NaN elsewhere when rounding pushes it past 1).
+ * Q == 0 launches nothing.  CATRE_ERR_BAD_ARG: a null array that would be read or written, T / G < 1, a negative size,
+ * T * Q beyond int32. */
+int catre_eval_overlaps(const float* pred_pose, const float* pred_scale, const int32_t* pred_idx, const float* gt_pose,
+                        const float* gt_scale, const int32_t* gt_hv, const int32_t* pred_off, const int32_t* gt_off,
+                        const int32_t* pair_off, const int32_t* pair_group, const int32_t* group_mode,
+                        const double* cos_sin, float* iou, double* degcm, int T, int N, int P, int NG, int G, int Q,
+                        void* stream);
+/* Greedy IoU matching of every (iteration, group, threshold) (compute_3d_matches :582-616): predictions in their stored
+ * order; each takes the not-yet-matched GT of largest IoU if that IoU is STRICTLY above thres[s]; an IoU equal to the
+ * threshold leaves prediction and GT free (:605-614); among equal IoUs the later GT wins (the reversed argsort of :591).
+ * thres: S doubles on the device.  pred_match [T, S, P] / gt_match [T, S, NG] int32: in-group index of the partner, -1
+ * without one; every element is written. */
+int catre_eval_match_iou(const float* iou, const int32_t* pred_off, const int32_t* gt_off, const int32_t* pair_off,
+                         const double* thres, int32_t* pred_match, int32_t* gt_match, int T, int S, int P, int NG, int G,
+                         int Q, void* stream);
+/* Pose matching of every (iteration, group, degree threshold, shift threshold) (compute_match_from_degree_cm :715-757)
+ * among the predictions and GTs that catre_eval_match_iou paired at threshold index sel < S (use_matches_for_pose,
+ * :855-880); sel = -1: among all (iou_pred_match / iou_gt_match are then not read and may be NULL).  Each prediction, in
+ * order, takes the unmatched GT of smallest degree + cm among those with degree <= deg_thres[d] and cm <= cm_thres[c]
+ * (equal sums: the earlier GT).  pose_pred_match [T, D, C, P] / pose_gt_match [T, D, C, NG] int32: index of the partner
+ * WITHIN THE SELECTED SUBSET of its group (the reference's compacted arrays), -1 without one, -2 for an object outside
+ * the subset; every element is written. */
+int catre_eval_match_pose(const double* degcm, const int32_t* pred_off, const int32_t* gt_off, const int32_t* pair_off,
+                          const int32_t* iou_pred_match, const int32_t* iou_gt_match, int S, int sel,
+                          const double* deg_thres, const double* cm_thres, int32_t* pose_pred_match,
+                          int32_t* pose_gt_match, int T, int D, int C, int P, int NG, int G, int Q, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
