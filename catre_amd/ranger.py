@@ -7,6 +7,11 @@ launches (``catre_op_ranger_step``) instead of ~1000 tiny torch ops per step, K 
 train loop's ``nan_to_num(grad, nan=0, posinf=1e5, neginf=-1e5)`` (``core/catre/engine/engine.py:351-353``) can
 be folded into the same pass with ``clean_grads=True``.
 
+One quirk of the reference is kept on purpose: ``use_gc`` is stored (and readable as ``self.use_gc``) but never
+consulted.  The reference's ``step()`` centralizes every gradient with ``grad.dim() > gc_gradient_threshold``
+(``ranger.py:146``; the threshold is 1, or 3 with ``gc_conv_only=True``) whatever the flag says, so
+``use_gc=False`` still centralizes - here too, or a run resumed from the other class's checkpoint would diverge.
+
 The scalar RAdam rectification terms (N_sma, step size) are computed on the host in double precision exactly
 like the reference; everything per element runs on the device in fp32.  ``step()`` is split in two halves so that a
 captured HIP graph can replay it: :meth:`prepare_step` (host only: advances the step counters and fills a pinned
@@ -108,7 +113,7 @@ class Ranger(Optimizer):
                 t = terms.get(step)
                 if t is None:
                     t = terms[step] = self._step_terms(step, beta1, beta2)
-                gc = self.use_gc and p.dim() > self.gc_gradient_threshold
+                gc = p.dim() > self.gc_gradient_threshold   # use_gc is not consulted: the reference's step() never does
                 n = p.numel()
                 ps.append(p), gs.append(g), sts.append(st)
                 c_lr.append(t[0] * lr), c_wd.append(wd * lr), c_ad.append(int(t[1])), c_look.append(int(step % k == 0))

@@ -465,6 +465,60 @@ def make_ranger_golden():
     print(f"ranger_steps: wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
 
 
+# Option variants of the Ranger fixture ``ranger_options.npz``: constructor arguments (``ctor``), the two param groups
+# (tensor indices into RANGER_SHAPES, lr, weight decay, optional per-group k), ``none``: {tensor: steps (0-based) at
+# which its gradient is None}, ``clean``: whether the train loop's nan_to_num runs on the gradients first.
+_RG = (dict(idx=(0, 1, 2), lr=2e-2, wd=0.0), dict(idx=(3, 4), lr=5e-3, wd=0.1))
+RANGER_VARIANTS = {
+    "no_gc": dict(ctor=dict(use_gc=False), groups=_RG),
+    "conv_only": dict(ctor=dict(gc_conv_only=True), groups=_RG),
+    "alpha_k": dict(ctor=dict(alpha=0.8), groups=(dict(_RG[0], k=3), dict(_RG[1], k=5))),
+    "sma4": dict(ctor=dict(N_sma_threshhold=4), groups=_RG),
+    "betas_eps": dict(ctor=dict(betas=(0.9, 0.99), eps=1e-8), groups=_RG),
+    "weight_decay": dict(ctor=dict(), groups=(dict(_RG[0], wd=0.05), dict(_RG[1], wd=0.2))),
+    "none_grad": dict(ctor=dict(), groups=_RG, none={1: (0, 1, 2, 8)}),
+    "no_clean": dict(ctor=dict(), groups=_RG, clean=False),
+}
+
+
+def ranger_variant_groups(params, variant):
+    """The param-group dicts of one variant for any Ranger class with the reference's constructor."""
+    return [dict(params=[params[i] for i in g["idx"]], lr=g["lr"], weight_decay=g["wd"], **({"k": g["k"]} if "k" in g else {}))
+            for g in variant["groups"]]
+
+
+def make_ranger_options_golden():
+    """The reference's own Ranger class stepped on CPU once per entry of RANGER_VARIANTS: parameters after every step,
+    final exp_avg / exp_avg_sq / slow_buffer / step.  Tensors that never took a step store no state."""
+    ref_shim.install()
+    from lib.torch_utils.solver.ranger import Ranger
+    from lib.torch_utils.misc import nan_to_num
+
+    out = {}
+    for name, var in RANGER_VARIANTS.items():
+        params, grads = ranger_problem()
+        ps = [torch.nn.Parameter(p.clone()) for p in params]
+        opt = Ranger(ranger_variant_groups(ps, var), lr=1e-2, **var["ctor"])
+        for t in range(RANGER_STEPS):
+            for i, (p, g) in enumerate(zip(ps, grads[t])):
+                if t in var.get("none", {}).get(i, ()):
+                    p.grad = None
+                    continue
+                p.grad = g.clone()
+                if var.get("clean", True):
+                    nan_to_num(p.grad, nan=0, posinf=1e5, neginf=-1e5, out=p.grad)
+            opt.step()
+            for i, p in enumerate(ps):
+                out[f"{name}/p{i}_step{t + 1}"] = _np(p.data)
+        for i, p in enumerate(ps):
+            st = opt.state[p]
+            out[f"{name}/exp_avg{i}"], out[f"{name}/exp_avg_sq{i}"] = _np(st["exp_avg"]), _np(st["exp_avg_sq"])
+            out[f"{name}/slow{i}"], out[f"{name}/step{i}"] = _np(st["slow_buffer"]), np.int64(st["step"])
+    path = os.path.join(GOLDEN_DIR, "ranger_options.npz")
+    np.savez_compressed(path, **out)
+    print(f"ranger_options: wrote {path} ({os.path.getsize(path) / 1024:.0f} KiB)")
+
+
 def make_rot_mats_golden(seed=41, B=24):
     """a10: the reference's ``get_rot_mat`` (models/model_utils.py:28-40) for every rotation type on seeded residuals
     (O(1) values, small-angle rows on both sides of the reference's thresholds, one exact zero), its autograd gradient
@@ -532,6 +586,9 @@ def main(argv=None):
     if "ranger" in names:
         make_ranger_golden()
         names = [n for n in names if n != "ranger"]
+    if "ranger_options" in names:
+        make_ranger_options_golden()
+        names = [n for n in names if n != "ranger_options"]
     if "pcl" in names:
         make_pcl_golden()
         names = [n for n in names if n != "pcl"]
@@ -551,6 +608,7 @@ def main(argv=None):
     if not (argv or sys.argv[1:]):
         names = names + list(TRAIN_CASES)
         make_ranger_golden()
+        make_ranger_options_golden()
         make_amp_golden()
         for n in TRAIN_CASES:
             make_amp_train_golden(n)

@@ -1,7 +1,7 @@
 """ORACLE (test infrastructure only) - functional restatement of the reference's Ranger update,
 ``lib/torch_utils/solver/ranger.py:102-202`` (RAdam + Lookahead + gradient centralization), and of the train
 loop's gradient clean-up ``core/catre/engine/engine.py:351-353``.  Pinned to the reference class itself through
-``tests/golden/ranger_steps.npz`` (``oracle/make_golden.py``)."""
+``tests/golden/ranger_steps.npz`` and, option by option, ``tests/golden/ranger_options.npz`` (``oracle/make_golden.py``)."""
 import math
 
 import torch
@@ -22,14 +22,16 @@ def ranger_step(p, grad, state, lr, betas=(0.95, 0.999), eps=1e-5, weight_decay=
                 use_gc=True, gc_threshold=1, storage=None):
     """One update of one tensor; ``state`` is a dict that this function creates / advances in place.
     ``storage`` (e.g. torch.float32): round the parameter and the slow weights to that dtype where the reference, whose
-    tensors ARE fp32, stores them (after the RAdam update, after the lookahead merge) - arithmetic stays in p's dtype."""
+    tensors ARE fp32, stores them (after the RAdam update, after the lookahead merge) - arithmetic stays in p's dtype.
+    ``use_gc`` is accepted and ignored, as in the reference: its ``step()`` centralizes whenever
+    ``grad.dim() > gc_gradient_threshold`` (ranger.py:146) and only stores / logs the flag (ranger.py:87-96)."""
     def stored(t):
         return t if storage is None else t.to(storage).to(t.dtype)
     if not state:
         state.update(step=0, exp_avg=torch.zeros_like(p), exp_avg_sq=torch.zeros_like(p), slow_buffer=p.clone())
     beta1, beta2 = betas
     g = grad.clone()
-    if use_gc and g.dim() > gc_threshold:
+    if g.dim() > gc_threshold:
         g = g - g.mean(dim=tuple(range(1, g.dim())), keepdim=True)
     state["step"] += 1
     state["exp_avg_sq"] = state["exp_avg_sq"] * beta2 + (1 - beta2) * g * g

@@ -1,15 +1,17 @@
 """f4: Ranger.  CPU: the oracle restatement vs the reference class (golden).  GPU: the fused multi-tensor HIP step
 (with nan_to_num folded in) vs the same golden after every one of 14 steps (lookahead merges at 6 and 12, the RAdam
-rectification switches on at step 6), plus optimizer-state parity."""
+rectification switches on at step 6), plus optimizer-state parity.  The oracle is also held to the reference class's
+recorded runs under every constructor option (ranger_options.npz); the fused step's side of that, its tiling edges and
+its exact invariances are in tests/test_ranger_edges.py."""
 import os
 
 import numpy as np
 import pytest
 import torch
 
-from oracle.make_golden import RANGER_SHAPES, RANGER_STEPS, ranger_problem
+from oracle.make_golden import RANGER_SHAPES, RANGER_STEPS, RANGER_VARIANTS, ranger_problem
 from oracle.ranger_oracle import clean_grad, ranger_step
-from tests.util import GOLDEN_DIR
+from tests.util import GOLDEN_DIR, assert_close_same_nonfinite, ranger_options_golden as options_golden
 
 GROUPS = [dict(idx=(0, 1, 2), lr=2e-2, wd=0.0), dict(idx=(3, 4), lr=5e-3, wd=0.1)]
 
@@ -31,6 +33,55 @@ def test_ranger_oracle_matches_reference_class():
     for i, st in enumerate(states):
         np.testing.assert_allclose(st["exp_avg_sq"].numpy(), z[f"exp_avg_sq{i}"], rtol=2e-5, atol=1e-7)
         np.testing.assert_allclose(st["slow_buffer"].numpy(), z[f"slow{i}"], rtol=2e-5, atol=2e-6)
+
+
+def variant_grad(var, grads, t, i):
+    """The gradient tensor i sees at step t (0-based) of a fixture variant: None, raw, or cleaned like the train loop."""
+    if t in var.get("none", {}).get(i, ()):
+        return None
+    return clean_grad(grads[t][i]) if var.get("clean", True) else grads[t][i].clone()
+
+
+@pytest.mark.parametrize("name", list(RANGER_VARIANTS))
+def test_ranger_oracle_matches_reference_options(name):
+    """Every constructor option the reference class reads (and use_gc, which it does not), a gradient that is None in
+    some steps, and uncleaned NaN / inf gradients: the oracle vs the reference class's recorded run."""
+    z, var = options_golden(), RANGER_VARIANTS[name]
+    ctor = var["ctor"]
+    params, grads = ranger_problem()
+    states = [dict() for _ in params]
+    kw = dict(betas=ctor.get("betas", (0.95, 0.999)), eps=ctor.get("eps", 1e-5), alpha=ctor.get("alpha", 0.5),
+              threshold=ctor.get("N_sma_threshhold", 5), use_gc=ctor.get("use_gc", True),
+              gc_threshold=3 if ctor.get("gc_conv_only", False) else 1)
+    for t in range(RANGER_STEPS):
+        for grp in var["groups"]:
+            for i in grp["idx"]:
+                g = variant_grad(var, grads, t, i)
+                if g is not None:
+                    params[i] = ranger_step(params[i], g, states[i], grp["lr"], weight_decay=grp["wd"], k=grp.get("k", 6), **kw)
+        for i, p in enumerate(params):
+            assert_close_same_nonfinite(p.numpy(), z[f"{name}/p{i}_step{t + 1}"], 2e-5, 2e-6, f"{name} p{i} step {t + 1}")
+    for i, st in enumerate(states):
+        assert st["step"] == int(z[f"{name}/step{i}"]) == RANGER_STEPS - len(var.get("none", {}).get(i, ()))
+        assert_close_same_nonfinite(st["exp_avg"].numpy(), z[f"{name}/exp_avg{i}"], 2e-5, 2e-6, f"{name} exp_avg{i}")
+        assert_close_same_nonfinite(st["exp_avg_sq"].numpy(), z[f"{name}/exp_avg_sq{i}"], 2e-5, 1e-7, f"{name} exp_avg_sq{i}")
+        assert_close_same_nonfinite(st["slow_buffer"].numpy(), z[f"{name}/slow{i}"], 2e-5, 2e-6, f"{name} slow{i}")
+
+
+def test_ranger_options_fixture_has_what_it_is_for():
+    """The fixture must not pass vacuously: the no-clean-up run really carries NaN / +inf and each option really moves
+    the trajectory away from the default run of ranger_steps.npz."""
+    z, z0 = options_golden(), _golden()
+    last = f"step{RANGER_STEPS}"
+    assert np.isnan(z[f"no_clean/p1_{last}"][0]).all() and np.isfinite(z[f"no_clean/p1_{last}"][1:]).all()
+    assert np.isposinf(z["no_clean/p4_step5"][2]).sum() == 39 and np.isnan(z["no_clean/p4_step5"][2, 5])
+    assert np.isnan(z[f"no_clean/p0_{last}"][1]).all()
+    moved = dict(conv_only=1, alpha_k=0, sma4=0, betas_eps=0, weight_decay=0, none_grad=1)
+    for name, i in moved.items():
+        assert np.abs(z[f"{name}/p{i}_{last}"] - z0[f"p{i}_{last}"]).max() > 1e-4, name
+    # use_gc=False is the reference's no-op: the recorded run equals the default one bit for bit
+    for i in range(len(RANGER_SHAPES)):
+        np.testing.assert_array_equal(z[f"no_gc/p{i}_{last}"], z0[f"p{i}_{last}"])
 
 
 @pytest.mark.gpu

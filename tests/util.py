@@ -55,3 +55,16 @@ def load_train_golden(name):
     sym_info = [y_axis_symmetries(nsym) if i in sym_idx else None for i in range(B)]
     ref = {k: z[k] for k in z.files if not k.startswith(("in_", "meta"))}
     return dict(B=B, N=N, M=M, seed=seed, salt=salt, cfg=cfg, batch=batch, sym_info=sym_info, ref=ref)
+
+
+def ranger_options_golden():
+    return np.load(os.path.join(GOLDEN_DIR, "ranger_options.npz"))
+
+
+def assert_close_same_nonfinite(got, want, rtol, atol, msg):
+    """NaN, +inf and -inf at exactly the same positions; the finite entries within rtol / atol."""
+    got, want = np.asarray(got), np.asarray(want)
+    for kind, f in (("NaN", np.isnan), ("+inf", np.isposinf), ("-inf", np.isneginf)):
+        np.testing.assert_array_equal(f(got), f(want), err_msg=f"{msg}: {kind} positions")
+    fin = np.isfinite(want)
+    np.testing.assert_allclose(got[fin], want[fin], rtol=rtol, atol=atol, err_msg=msg)
