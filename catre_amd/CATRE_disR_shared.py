@@ -92,8 +92,16 @@ class CATRE_disR_shared(nn.Module):
         if self._rt is None:
             num_points = self.rot_head.num_points
             n = int(self.cfg.INPUT.get("NUM_PCL", num_points // 2))
-            self._rt = HipRuntime(lambda: dict(self.named_parameters()), n, num_points - n, self._opts.ts_in_dim, root=self)
+            self._rt = HipRuntime(lambda: dict(self.named_parameters()), n, num_points - n, self._opts.ts_in_dim, root=self,
+                                  forms=self._head_forms())
         return self._rt
+
+    def _head_forms(self):
+        """(rot head, ts head) ``heads.HeadForm``: width, depth, norm and activation as configured (``INIT_CFG``).  The
+        shipped form runs on the fused kernels; any other layer by layer on the generic norm + activation ops."""
+        from .heads import SHIPPED_FORM
+
+        return getattr(self.rot_head, "form", SHIPPED_FORM), getattr(self.ts_head, "form", SHIPPED_FORM)
 
     def _named_live_params(self):
         """`dict(self.named_parameters())` without walking the module tree on every forward (0.25 ms of a 4 ms host
@@ -150,6 +158,7 @@ class CATRE_disR_shared(nn.Module):
         if self.cfg.MODEL.CATRE.get("COMPUTE_DTYPE", None) in _FP16_NAMES:
             raise NotImplementedError("MODEL.CATRE.COMPUTE_DTYPE='fp16' is an inference mode (no_grad, do_loss=False, "
                                       "refine); the training forward runs in 'bf16', 'split' or 'fp32'")
+        rt = self._runtime()
         from .train_forward import forward_train
         from .train_ops import amp_mode, train_kernels
 
@@ -158,7 +167,7 @@ class CATRE_disR_shared(nn.Module):
         with amp_mode(self.cfg.MODEL.CATRE.get("COMPUTE_DTYPE", None)), \
                 train_kernels(self.cfg.MODEL.CATRE.get("TRAIN_KERNELS", None)):
             pose, scale, aux = forward_train(live, self._opts, x, tfd_kps, init_pose, init_scale, K_zoom, mean_scales,
-                                             rt=self._runtime())
+                                             rt=rt, forms=rt.forms if rt.layered else None)
         out_dict = {f"pose_{cur_iter}": pose, f"scale_{cur_iter}": scale}
         if not do_loss:
             return out_dict
@@ -342,20 +351,27 @@ def expected_state_shapes(cfg):
         s[f"pcl_net.{name}.weight"], s[f"pcl_net.{name}.bias"] = (o, i, 1), (o,)
     if ft:
         stn("pcl_net.fstn", 64)
+    def head(p, init, layers, in_dim, norm_default):
+        F, L = int(init.get("feat_dim", 256)), int(init.get("num_layers", 2))
+        gn = init.get("norm", norm_default) == "GN"   # (the classes' own defaults: ConvOutPerRotHead "GN", FC_TransSizeHead "none")
+        if gn:
+            s[f"{p}.norm.weight"], s[f"{p}.norm.bias"] = (F,), (F,)
+        for i in range(L):
+            k = in_dim if i == 0 else F
+            s[f"{p}.{layers}.{3 * i}.weight"] = (F, k, 1) if layers == "layers" else (F, k)
+            s[f"{p}.{layers}.{3 * i}.bias"] = (F,)
+            if gn:
+                s[f"{p}.{layers}.{3 * i + 1}.weight"], s[f"{p}.{layers}.{3 * i + 1}.bias"] = (F,), (F,)
+        return F
+
     for a in ("x", "y"):
         p = f"rot_head.rot_head_{a}"
-        s[f"{p}.norm.weight"], s[f"{p}.norm.bias"] = (256,), (256,)
-        s[f"{p}.layers.0.weight"], s[f"{p}.layers.0.bias"] = (256, 1088, 1), (256,)
-        s[f"{p}.layers.1.weight"], s[f"{p}.layers.1.bias"] = (256,), (256,)
-        s[f"{p}.layers.3.weight"], s[f"{p}.layers.3.bias"] = (256, 256, 1), (256,)
-        s[f"{p}.layers.4.weight"], s[f"{p}.layers.4.bias"] = (256,), (256,)
-        s[f"{p}.neck.0.weight"], s[f"{p}.neck.0.bias"] = (rd, 256, 1), (rd,)
-        s[f"{p}.conv_p.weight"], s[f"{p}.conv_p.bias"] = (1, P, 1), (1,)
-    s["ts_head.norm.weight"], s["ts_head.norm.bias"] = (256,), (256,)
-    s["ts_head.linears.0.weight"], s["ts_head.linears.0.bias"] = (256, ts_in), (256,)
-    s["ts_head.linears.1.weight"], s["ts_head.linears.1.bias"] = (256,), (256,)
-    s["ts_head.linears.3.weight"], s["ts_head.linears.3.bias"] = (256, 256), (256,)
-    s["ts_head.linears.4.weight"], s["ts_head.linears.4.bias"] = (256,), (256,)
+        F = head(p, net.ROT_HEAD.INIT_CFG, "layers", 1088, "GN")
+        s[f"{p}.neck.0.weight"], s[f"{p}.neck.0.bias"] = (rd, F, 1), (rd,)
+        s[f"{p}.conv_p.weight"] = (1, P, 1)
+        if net.ROT_HEAD.INIT_CFG.get("point_bias", True):
+            s[f"{p}.conv_p.bias"] = (1,)
+    F = head("ts_head", net.TS_HEAD.INIT_CFG, "linears", ts_in, "none")
     for n in ("fc_t", "fc_s"):
-        s[f"ts_head.{n}.weight"], s[f"ts_head.{n}.bias"] = (3, 256), (3,)
+        s[f"ts_head.{n}.weight"], s[f"ts_head.{n}.bias"] = (3, F), (3,)
     return s

@@ -1565,6 +1565,7 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 #include "catre_gram.h"
 #include "catre_small.h"
 #include "catre_train.h"
+#include "catre_heads.h"
 #include "catre_aug.h"
 #include "catre_pcl.h"
 #include "catre_loss.h"
@@ -2769,6 +2770,7 @@ int catre_colmax(const float* x, float* out, int B, int C, int N, void* stream) 
 }
 
 #include "catre_train_api.inc"
+#include "catre_heads_api.inc"
 
 // ---- row f2: train-time batch glue --------------------------------------------------------------------------
 int catre_aug_points(const float* pcl, const float* pose, const float* scale, const int32_t* sym_flags,

@@ -31,10 +31,23 @@ _INPUTS = ("x", "tfd_kps", "init_pose", "init_scale", "K_zoom", "gt_ego_rot", "g
            "mean_scales")
 
 
+def _require_shipped_heads(model, what):
+    """The captured chains are the fused ones: heads of another form run a host-side layer loop that is not captured."""
+    forms = getattr(model, "_head_forms", None)
+    if forms is not None:
+        from .heads import SHIPPED_FORM
+
+        if any(f != SHIPPED_FORM for f in forms()):
+            raise NotImplementedError(f"{what} captures the fused kernels of the shipped head form (feat_dim=256, "
+                                      "num_layers=2, GN with 32 groups, gelu); with heads of another form call "
+                                      "model.refine / model.forward directly (fp32, bf16 / autocast or split)")
+
+
 class GraphedTrainStep:
     def __init__(self, model, optimizer, example, sym_info, max_sym=None, warmup=3, amp=False):
         if not isinstance(optimizer, Ranger):
             raise TypeError("GraphedTrainStep needs the fused catre_amd.ranger.Ranger (its step is capturable)")
+        _require_shipped_heads(model, "GraphedTrainStep")
         self.model, self.opt, self.amp = model, optimizer, bool(amp)
         dev = example["x"].device
         self.static = {k: example[k].detach().clone().contiguous() for k in _INPUTS if example.get(k) is not None}
@@ -167,6 +180,7 @@ class GraphedRefine:
     """
 
     def __init__(self, model, example, n_iter=None, warmup=2):
+        _require_shipped_heads(model, "GraphedRefine")
         self.model = model
         self.n_iter = int(model.cfg.MODEL.CATRE.N_ITER_TEST if n_iter is None else n_iter)
         self.keys = [k for k in _REFINE_INPUTS if example.get(k) is not None]

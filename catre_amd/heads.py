@@ -4,11 +4,20 @@ driver (the concatenated feature tensors are never built); called on their own -
 they run layer by layer on the HIP training ops (``catre_amd/train_ops.py``), autograd included.
 
 Mirrors ``core/catre/models/heads/conv_out_per_rot_head.py`` and ``fc_trans_size_head.py``:
-same class names, constructor kwargs, ModuleList indices (``layers.0/1/3/4``, ``linears.0/1/3/4``),
-never-used ``norm`` GroupNorm, and initialisation (N(0, 0.001^2) conv/linear weights, zero bias,
-GN weight 1; ``fc_t``/``fc_s`` N(0, 0.01^2)), so reference checkpoints load ``strict=True``.
+same class names, constructor kwargs, three ModuleList slots per layer (``layers.{3i}`` conv, ``{3i+1}`` GroupNorm or
+Identity, ``{3i+2}`` the shared activation module; ``linears`` likewise), never-used ``norm`` attribute, and initialisation
+(N(0, 0.001^2) conv/linear weights, zero bias, GN weight 1; ``fc_t``/``fc_s`` N(0, 0.01^2)), so reference checkpoints load
+``strict=True``.
+
+Width (``feat_dim``: multiples of 8 up to 1024), depth, ``norm`` GN / none with any dividing ``num_gn_groups`` and ``act``
+relu / lrelu / silu / gelu / mish / none are all built (:class:`HeadForm`).  The shipped form keeps the kernels written for
+it; any other runs its norm + activation on the generic ops (``train_ops.gn_points_act`` / ``gn_rows_act``).
 """
+import typing
+
 import torch.nn as nn
+
+from . import hip
 
 def _normal_init(m, std):
     nn.init.normal_(m.weight, 0.0, std)
@@ -16,18 +25,83 @@ def _normal_init(m, std):
         nn.init.constant_(m.bias, 0.0)
 
 
-def _get_norm(norm, channels, num_gn_groups):
+class HeadForm(typing.NamedTuple):
+    """What the norm + activation kernels need to know about a head: width, depth, GroupNorm on / off and its group count,
+    activation (``hip.ACT_*``)."""
+    feat_dim: int
+    num_layers: int
+    norm: bool
+    groups: int
+    act: int
+
+
+SHIPPED_FORM = HeadForm(256, 2, True, 32, hip.ACT_GELU)   # every shipped config: the fused kernels are built for it
+
+_BN_FAMILY = ("BN", "BN1d", "SyncBN", "FrozenBN", "nnSyncBN", "naiveSyncBN", "IN")
+_ACTS = {"relu": hip.ACT_RELU, "lrelu": hip.ACT_LRELU, "leaky_relu": hip.ACT_LRELU, "leakyrelu": hip.ACT_LRELU,
+         "silu": hip.ACT_SILU, "swish": hip.ACT_SILU, "gelu": hip.ACT_GELU, "mish": hip.ACT_MISH, "none": hip.ACT_NONE,
+         "": hip.ACT_NONE}
+_PARAM_ACTS = ("prelu", "aconc", "metaaconc", "smu")
+
+
+def _norm_on(norm):
+    """True: GroupNorm, False: none (layer_utils.get_norm:41-45); anything else is not built."""
     if norm is None or (isinstance(norm, str) and norm.lower() in ("", "none")):
-        return nn.Identity()
+        return False
     if norm == "GN":
-        return nn.GroupNorm(num_gn_groups, channels)
-    raise NotImplementedError(f"norm={norm!r}: the HIP heads implement GroupNorm ('GN'), as in every shipped config")
+        return True
+    if norm in _BN_FAMILY:
+        raise NotImplementedError(
+            f"norm={norm!r}: the HIP heads implement 'GN' and 'none'.  'BN' is BatchNorm2d, which the reference itself cannot "
+            "feed with the heads' 3-D tensors; 'BN1d' and the other batch / instance norms need batch statistics and running "
+            "buffers")
+    raise ValueError(f"Unknown norm: {norm!r} (the HIP heads implement 'GN' and 'none')")
+
+
+def _get_norm(norm, channels, num_gn_groups):
+    if not _norm_on(norm):
+        return nn.Identity()
+    return nn.GroupNorm(num_gn_groups, channels)   # ValueError when num_gn_groups does not divide channels
+
+
+def act_id(act):
+    """``hip.ACT_*`` of an activation name as ``layer_utils.get_nn_act_func:61-95`` spells them."""
+    if act is None:
+        return hip.ACT_NONE
+    a = act.lower()
+    if a in _ACTS:
+        return _ACTS[a]
+    if a in _PARAM_ACTS:
+        raise NotImplementedError(f"act={act!r}: activations with learned parameters (prelu, aconc, metaaconc, smu) are not "
+                                  "built; the HIP heads implement relu, lrelu, silu / swish, gelu, mish and none")
+    if a == "sigmoid":
+        raise NotImplementedError("act='sigmoid' is not built; the HIP heads implement relu, lrelu, silu / swish, gelu, mish "
+                                  "and none")
+    raise ValueError(f"Unknown activation function: {act}.")   # layer_utils.py:94
 
 
 def _get_act(act):
-    if act is not None and act.lower() == "gelu":
-        return nn.GELU()
-    raise NotImplementedError(f"act={act!r}: the HIP heads implement exact-erf GELU, as in every shipped config")
+    """The module ``get_nn_act_func`` returns (no parameters, so no state_dict key): slope 0.1 for the leaky ReLU, the
+    exact-erf GELU."""
+    i = act_id(act)
+    return {hip.ACT_NONE: nn.Identity, hip.ACT_RELU: lambda: nn.ReLU(inplace=True),
+            hip.ACT_LRELU: lambda: nn.LeakyReLU(negative_slope=0.1, inplace=True), hip.ACT_SILU: lambda: nn.SiLU(inplace=True),
+            hip.ACT_GELU: nn.GELU, hip.ACT_MISH: lambda: nn.Mish(inplace=True)}[i]()
+
+
+def _head_form(what, feat_dim, num_layers, norm, num_gn_groups, act, num_classes, norm_input, dropout):
+    if int(feat_dim) != feat_dim or feat_dim % 8 or not 8 <= feat_dim <= 1024:
+        raise NotImplementedError(f"{what}: feat_dim={feat_dim!r} - the HIP heads take any multiple of 8 in 8..1024")
+    if int(num_layers) != num_layers or num_layers < 1:
+        raise ValueError(f"{what}: num_layers={num_layers!r} must be an integer >= 1")
+    if num_classes != 1:
+        raise NotImplementedError(f"{what}: num_classes={num_classes} (class-aware heads) is not built: num_classes=1")
+    if norm_input:
+        raise NotImplementedError(f"{what}: norm_input=True (a BatchNorm1d on the input) is not built")
+    if dropout:
+        raise NotImplementedError(f"{what}: dropout=True is not built")
+    on = _norm_on(norm)
+    return HeadForm(int(feat_dim), int(num_layers), on, int(num_gn_groups) if on else 1, act_id(act))
 
 
 class RotHead(nn.Module):
@@ -37,15 +111,16 @@ class RotHead(nn.Module):
                  act="leaky_relu", num_classes=1, kernel_size=1, num_points=1, norm_input=False, dropout=False,
                  point_bias=True):
         super().__init__()
-        if (in_dim, feat_dim, num_layers, num_classes, kernel_size, num_gn_groups) != (1088, 256, 2, 1, 1, 32) or not (
-                1 <= int(rot_dim) <= 3):
-            raise NotImplementedError(
-                "HIP rot head is built for in_dim=1088, feat_dim=256, num_layers=2, rot_dim in {1,2,3} (3: rot6d, 2: quat), "
-                "kernel_size=1, num_gn_groups=32, num_classes=1; got "
-                f"{(in_dim, feat_dim, num_layers, rot_dim, num_classes, kernel_size, num_gn_groups)}"
-            )
-        if norm_input or dropout:
-            raise NotImplementedError("norm_input / dropout are not used by the shipped configs")
+        if kernel_size != 1:
+            raise NotImplementedError(f"HIP rot head: kernel_size={kernel_size} is not built (the heads are 1x1 convolutions)")
+        if in_dim != 1088:
+            raise NotImplementedError(f"HIP rot head: in_dim={in_dim} is not built - its input is cat(1024 pooled, 64 "
+                                      "point-feature) channels: in_dim=1088")
+        if not 1 <= int(rot_dim) <= 3:
+            raise NotImplementedError(f"HIP rot head: rot_dim={rot_dim} is not built - rot_dim in {{1,2,3}} (3: rot6d, "
+                                      "2: quat)")
+        self.form = _head_form("HIP rot head", feat_dim, num_layers, norm, num_gn_groups, act, num_classes, norm_input,
+                               dropout)
         self.norm = _get_norm(norm, feat_dim, num_gn_groups)  # never used in forward (reference :92)
         self.act_func = act_func = _get_act(act)
         self.num_classes = num_classes
@@ -68,18 +143,23 @@ class RotHead(nn.Module):
                 nn.init.constant_(m.bias, 0.0)
 
     def forward(self, x):
-        """x [B,1088,P] -> (r [B,rot_dim], feat [B,rot_dim,P]) like the reference (``:126-140``): conv -> GN -> GELU ->
-        conv -> GN -> GELU -> neck = feat -> conv_p over the points."""
+        """x [B,1088,P] -> (r [B,rot_dim], feat [B,rot_dim,P]) like the reference (``:126-140``): per layer conv -> norm ->
+        act, then neck = feat -> conv_p over the points."""
         from . import train_ops as T
 
         B, C, P = x.shape
         if P != self.conv_p.in_channels:
             raise ValueError(f"RotHead was built for {self.conv_p.in_channels} points, got {P}")
-        rows = x.permute(0, 2, 1).reshape(B * P, C)
-        y = T.linear(rows, self.layers[0].weight, self.layers[0].bias)
-        a = T.gn_points_gelu(y, self.layers[1].weight, self.layers[1].bias, B, P)
-        y = T.linear(a, self.layers[3].weight, self.layers[3].bias)
-        a = T.gn_points_gelu(y, self.layers[4].weight, self.layers[4].bias, B, P)
+        f = self.form
+        a = x.permute(0, 2, 1).reshape(B * P, C)
+        for i in range(f.num_layers):
+            y = T.linear(a, self.layers[3 * i].weight, self.layers[3 * i].bias)
+            if f == SHIPPED_FORM:
+                a = T.gn_points_gelu(y, self.layers[3 * i + 1].weight, self.layers[3 * i + 1].bias, B, P)
+            else:
+                gn = self.layers[3 * i + 1]
+                a = T.gn_points_act(y, gn.weight if f.norm else None, gn.bias if f.norm else None, B, P, f.groups, f.act,
+                                    f.norm)
         y3 = neck_rows(a, self.neck[0].weight, self.neck[0].bias)             # [B*P,3], columns >= rot_dim are zero
         r = T.weighted_point_sum(y3, self.conv_p.weight, self.conv_p.bias, B, P)
         rd = self.rot_dim
@@ -88,7 +168,7 @@ class RotHead(nn.Module):
 
 
 def neck_weight3(weight, bias):
-    """neck Conv1d(256 -> rot_dim) parameters as [3,256] / [3], zero-padded (differentiable) for the 3-column kernels."""
+    """neck Conv1d(feat_dim -> rot_dim) parameters as [3,feat_dim] / [3], zero-padded (differentiable) for the 3-column kernels."""
     import torch.nn.functional as F
 
     rd = weight.shape[0]
@@ -100,8 +180,8 @@ def neck_weight3(weight, bias):
 
 
 def neck_rows(a, weight, bias):
-    """neck Conv1d(256 -> rot_dim, k=1) on point rows, zero-padded to the 3 columns the point-sum kernels are built for
-    (pure data movement on [rot_dim,256] / [rot_dim]; gradients of the padding rows are dropped by autograd)."""
+    """neck Conv1d(feat_dim -> rot_dim, k=1) on point rows, zero-padded to the 3 columns the point-sum kernels are built for
+    (pure data movement on [rot_dim,feat_dim] / [rot_dim]; gradients of the padding rows are dropped by autograd)."""
     import torch.nn.functional as F
 
     from . import train_ops as T
@@ -126,6 +206,7 @@ class ConvOutPerRotHead(nn.Module):
                              num_points, norm_input, dropout, point_bias)
         self.rot_head_x = mk()
         self.rot_head_y = mk()
+        self.form = self.rot_head_x.form
         self.num_points = num_points
         self.rot_dim = rot_dim
 
@@ -146,10 +227,8 @@ class FC_TransSizeHead(nn.Module):
     def __init__(self, in_dim=1024, feat_dim=256, num_layers=2, rot_dim=4, norm="none", num_gn_groups=32,
                  act="leaky_relu", num_classes=1, norm_input=False, dropout=False):
         super().__init__()
-        if (feat_dim, num_layers, num_classes, num_gn_groups) != (256, 2, 1, 32):
-            raise NotImplementedError("HIP ts head is built for feat_dim=256, num_layers=2, num_gn_groups=32, num_classes=1")
-        if norm_input or dropout:
-            raise NotImplementedError("norm_input / dropout are not used by the shipped configs")
+        self.form = _head_form("HIP ts head", feat_dim, num_layers, norm, num_gn_groups, act, num_classes, norm_input,
+                               dropout)
         self.norm = _get_norm(norm, feat_dim, num_gn_groups)  # never used in forward (reference :28)
         self.act_func = act_func = _get_act(act)
         self.num_classes = num_classes
@@ -178,8 +257,13 @@ class FC_TransSizeHead(nn.Module):
         """x [B,in_dim] -> (trans deltas [B,3], scale deltas [B,3])."""
         from . import train_ops as T
 
-        h = T.linear(x.flatten(1), self.linears[0].weight, self.linears[0].bias)
-        h = T.gn_rows_gelu(h, self.linears[1].weight, self.linears[1].bias)
-        h = T.linear(h, self.linears[3].weight, self.linears[3].bias)
-        h = T.gn_rows_gelu(h, self.linears[4].weight, self.linears[4].bias)
+        f = self.form
+        h = x.flatten(1)
+        for i in range(f.num_layers):
+            h = T.linear(h, self.linears[3 * i].weight, self.linears[3 * i].bias)
+            gn = self.linears[3 * i + 1]
+            if f == SHIPPED_FORM:
+                h = T.gn_rows_gelu(h, gn.weight, gn.bias)
+            else:
+                h = T.gn_rows_act(h, gn.weight if f.norm else None, gn.bias if f.norm else None, f.groups, f.act, f.norm)
         return T.linear(h, self.fc_t.weight, self.fc_t.bias), T.linear(h, self.fc_s.weight, self.fc_s.bias)

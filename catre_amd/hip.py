@@ -62,6 +62,7 @@ ROWS_BF16 = 0x100   # CATRE_ROWS_BF16
 PACK_F32_ENCODER, PACK_F32_HEADS, PACK_BF16, PACK_SPLIT, PACK_F32_TAILS, PACK_ALL = 1, 2, 4, 8, 16, 31
 PACK_F16 = 32       # CATRE_PACK_F16: the fp16 packs DTYPE_F16 reads (not part of PACK_ALL)
 ROT_6D, ROT_QUAT, ROT_LOG_QUAT, ROT_LIE_VEC = 0, 1, 2, 3
+ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SILU, ACT_GELU, ACT_MISH = range(6)   # CATRE_ACT_*
 ROT_DIMS = {ROT_6D: 6, ROT_QUAT: 4, ROT_LOG_QUAT: 3, ROT_LIE_VEC: 3}
 
 
@@ -203,6 +204,14 @@ _SIGS = {
     "catre_op_gnp_gelu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _I, _I, _P]),
     "catre_op_gnr_gelu_fwd": (_I, [_P, _P, _P, _P, _I, _P]),
     "catre_op_gnr_gelu_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _I, _P]),
+    "catre_op_gnp_act_fwd": (_I, [_P] * 5 + [_I] * 6 + [_P]),
+    "catre_op_gnp_act_bwd_ws_bytes": (_SZ, [_I, _I, _I, _I]),
+    "catre_op_gnp_act_bwd": (_I, [_P] * 8 + [_I, _P, _SZ] + [_I] * 6 + [_P]),
+    "catre_op_gnr_act_fwd": (_I, [_P] * 4 + [_I] * 5 + [_P]),
+    "catre_op_gnr_act_bwd_ws_bytes": (_SZ, [_I, _I]),
+    "catre_op_gnr_act_bwd": (_I, [_P] * 7 + [_I, _P, _SZ] + [_I] * 5 + [_P]),
+    "catre_op_gnp_act_neck_wsum_ws_bytes": (_SZ, [_I, _I, _I]),
+    "catre_op_gnp_act_neck_wsum": (_I, [_P] * 9 + [_SZ] + [_I] * 7 + [_P]),
     "catre_op_wsum_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
     "catre_op_wsum_bwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _SZ, _I, _I, _P]),
     "catre_op_wsum_bwd_n": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _SZ, _I, _I, _P]),

@@ -59,13 +59,20 @@ class HipRuntime:
     the image is only read); a training stream next to a concurrent inference stream - or a ``GraphedRefine`` replay -
     on the SAME runtime is not supported: use a second model instance (``copy.deepcopy`` drops the runtime)."""
 
-    def __init__(self, named_params, N, M, ts_in_dim, root=None):
-        """``named_params``: callable returning ``{state_dict key: tensor}`` of the LIVE parameters.  ``root`` (optional):
+    def __init__(self, named_params, N, M, ts_in_dim, root=None, forms=None):
+        """``named_params``: callable returning ``{state_dict key: tensor}`` of the LIVE parameters.  ``forms`` (optional):
+        (rot head, ts head) ``heads.HeadForm``; with a head that is not the shipped form the fused head kernels and their
+        weight packs are not used (`layered`).  ``root`` (optional):
         the module whose ``named_parameters()`` keys are the state_dict keys as they are - lets ``_live_params`` read the
         parameters through cached ``module._parameters`` slots instead of walking the module tree on every call (the walk
         was 60 % of a forward's host time at B=1, profiles/eval_loop_cprofile.py)."""
         self._named_params = named_params
         self._root = root
+        from .heads import SHIPPED_FORM
+
+        self.forms = tuple(forms) if forms is not None else (SHIPPED_FORM, SHIPPED_FORM)
+        # a head of another form: the heads run layer by layer (train_forward.heads_rows), and the packs hold the encoder only
+        self.layered = any(f != SHIPPED_FORM for f in self.forms)
         self._slots = None
         self._links = None
         self.N, self.M, self.ts_in_dim = int(N), int(M), int(ts_in_dim)
@@ -79,6 +86,11 @@ class HipRuntime:
 
     # ------------------------------------------------------------------ weights
     def _live_params(self):
+        if self.layered:
+            # the C ABI's head slots describe the shipped form: left NULL (catre_pack_weights_sel skips a NULL source), so
+            # the packed image holds the encoder alone and no fused head kernel can be handed these weights
+            named = self._named_params()
+            return [named.get(k) if k.startswith("pcl_net.") else None for k in hip.PARAM_KEYS]
         if self._root is None:
             named = self._named_params()
             return [named.get(k) for k in hip.PARAM_KEYS]
@@ -188,6 +200,8 @@ class HipRuntime:
             assert Ks is not None and Ks.shape == (B, 3, 3)  # pose_scale_from_delta_init.py:64
         if opts.scale_base_mean and ms is None:
             raise ValueError("SCLAE_TYPE without 'iter' needs mean_scales")
+        if self.layered:
+            return self._refine_iter_layered(x, tfd_kps, init_pose, init_scale, Ks, ms, opts)
         prm, packed = self.params(dev, self._refine_packs(opts))
         ws = self.workspace(B, N, M, dev)
         pose_out = torch.empty(B, 3, 4, dtype=torch.float32, device=dev)
@@ -216,10 +230,18 @@ class HipRuntime:
             raise ValueError("T_TRANSFORM_K_AWARE needs K")
         if opts.scale_base_mean and ms is None:
             raise ValueError("SCLAE_TYPE without 'iter' needs mean_scales")
-        prm, packed = self.params(dev, self._refine_packs(opts))
-        ws = self.workspace(B, N, M, dev)
         poses = torch.empty(n_iter + 1, B, 3, 4, dtype=torch.float32, device=dev)
         scales = torch.empty(n_iter + 1, B, 3, dtype=torch.float32, device=dev)
+        if self.layered:
+            # heads of another form than the shipped one: the K loop runs here - catre_pose_apply, the fused inference
+            # encoder, the heads layer by layer, catre_pose_update - and saves nothing for a backward
+            poses[0], scales[0] = init_pose, init_scale
+            for i in range(n_iter):
+                x, tfd_kps = pose_apply(pcl, obj_kps, poses[i], scales[i], zero_center=bool(opts.zero_center))
+                poses[i + 1], scales[i + 1] = self._refine_iter_layered(x, tfd_kps, poses[i], scales[i], Ks, ms, opts)
+            return poses, scales
+        prm, packed = self.params(dev, self._refine_packs(opts))
+        ws = self.workspace(B, N, M, dev)
         # slot 0 (the reference's out_dict["pose_0"], catre_evaluator.py:292) is written by iteration 1's pose-update kernel:
         # no copy launch inside a refine
         init_pose, init_scale = init_pose.contiguous(), init_scale.contiguous()
@@ -230,6 +252,31 @@ class HipRuntime:
             "catre_refine_k_from",
         )
         return poses, scales
+
+    _LAYERED_MODES = {hip.DTYPE_F32: "fp32", hip.DTYPE_BF16: "bf16", hip.DTYPE_SPLIT: "split"}
+
+    def _refine_iter_layered(self, x, tfd_kps, init_pose, init_scale, Ks, ms, opts):
+        """One no-grad forward with heads that are not the shipped form: the encoder on the fused inference kernels (fp32;
+        the packed image holds the encoder alone), the heads layer by layer - their linears in ``opts.compute_dtype`` the
+        way ``train_ops.linear`` handles it, norm + activation in fp32, each RotHead's tail as one op
+        (``catre_op_gnp_act_neck_wsum``) - then ``catre_pose_update``."""
+        from . import train_forward as TF
+        from . import train_ops as T
+
+        mode = self._LAYERED_MODES.get(int(opts.compute_dtype))
+        if mode is None:
+            raise NotImplementedError("MODEL.CATRE.COMPUTE_DTYPE='fp16' is built for the shipped head form (feat_dim=256, "
+                                      "num_layers=2, GN with 32 groups, gelu); heads of another form run in 'fp32', 'bf16' "
+                                      "(or torch.autocast) and 'split'")
+        B, N, M = x.shape[0], x.shape[2], tfd_kps.shape[2]
+        with torch.no_grad(), T.amp_mode(mode):
+            st = self.stage_pointnet(x, tfd_kps, feature_transform=bool(opts.feature_transform))
+            g, pfmax = st["gfeat"][:, :1024], st["gfeat"][:, 1024:]
+            pf_obj = T.object_major(st["pointfeat"], B, N, M)
+            p = {k: v.detach() for k, v in self._named_params().items()}
+            rot, dt, ds = TF.heads_rows(p, opts, self.forms, g, pfmax, pf_obj, init_pose, init_scale, B, N, M,
+                                        fused_tail=True)
+            return pose_update(rot, dt, ds, init_pose, init_scale, ms, Ks, opts)
 
     def _check_nm(self, N, M):
         if N + M != self.N + self.M:
@@ -325,7 +372,8 @@ class HipRuntime:
             M = tfd_kps.shape[2]
             pts = hip.points_desc(x, tfd_kps)
         C = 2 * B if M > 0 else B
-        prm, packed = self.params(dev)
+        # (heads of another form than the shipped one: the image holds the fp32 encoder packs alone)
+        prm, packed = self.params(dev, hip.PACK_F32_ENCODER if self.layered else hip.PACK_ALL)
         named = {k: t for k, t in zip(hip.PARAM_KEYS, self._param_keep)}
         ws = self.workspace(B, N, M, dev)
         st = hip.stream_ptr(dev)

@@ -13,6 +13,7 @@ and throughput are measured on procedurally generated inputs of the reference's 
   initial pose/scale, NOCS intrinsics (values from reference ``ref/nocs.py:103``).
 """
 import math
+import re
 import zlib
 
 import torch
@@ -70,7 +71,8 @@ def recipe_tensor(key, shape, salt=0):
         if len(shape) == 1:  # GroupNorm gamma
             return 1.0 + 0.1 * r
         return r / math.sqrt(fan_in)
-    if len(shape) == 1 and (".layers.1." in key or ".layers.4." in key or ".linears.1." in key or ".linears.4." in key):
+    m = re.search(r"\.(?:layers|linears)\.(\d+)\.", key)
+    if len(shape) == 1 and m is not None and int(m.group(1)) % 3 == 1:   # slot 3i+1 of a head's ModuleList: layer i's norm
         return 0.1 * r  # GroupNorm beta
     return 0.05 * r
 
@@ -78,6 +80,19 @@ def recipe_tensor(key, shape, salt=0):
 def recipe_state_dict(shapes, salt=0):
     """``shapes``: mapping key -> shape (e.g. ``{k: v.shape for k, v in model.state_dict().items()}``)."""
     return {k: recipe_tensor(k, tuple(s), salt) for k, s in sorted(shapes.items())}
+
+
+def head_case_inputs(kind, B, dim, rot_dim, seed):
+    """Seeded input and output cotangents of a stand-alone head (tests/golden/head_forms.npz holds results only; the tool
+    that writes it and the tests both call this).  kind "rot": x [B,1088,dim points], cotangents of (r [B,rot_dim], feat
+    [B,rot_dim,dim]); kind "ts": x [B,dim], cotangents of (trans [B,3], scale [B,3])."""
+    g = torch.Generator(device="cpu")
+    g.manual_seed(7 + 104729 * seed)
+    if kind == "rot":
+        x = 0.5 * torch.randn(B, 1088, dim, generator=g)
+        return x, (torch.randn(B, rot_dim, generator=g), 0.1 * torch.randn(B, rot_dim, dim, generator=g))
+    x = 0.5 * torch.randn(B, dim, generator=g)
+    return x, (torch.randn(B, 3, generator=g), torch.randn(B, 3, generator=g))
 
 
 def _quat_to_mat(q):

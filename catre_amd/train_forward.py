@@ -161,6 +161,65 @@ def _rot_head(g, pf_obj, p, prefix, B, N, M, x_cm=False):
     return _first_cols(T.weighted_point_sum(y3, w("conv_p.weight"), p.get(f"{prefix}.conv_p.bias"), B, P), rd)
 
 
+def _rot_head_form(g, pf_obj, p, prefix, B, N, M, form, fused_tail=False):
+    """RotHead.forward for a head of any configured form (``heads.HeadForm``: width, depth, GroupNorm on / off and groups,
+    activation).  Layer 0 keeps the restructuring of the shipped route at any width: the global half ``W0[:, :1024] g`` is a
+    per-cloud bias, the point half runs on pointfeat - the ``[B,1088,P]`` tensor is never built.  The matrix work is
+    ``T.linear`` / ``T.linear_cloudbias`` (tiled MFMA kernel at widths 32..256 in steps of 32, 512 and 1024; the small
+    GEMM - correct, slow - elsewhere), norm + activation the generic ops.  fused_tail (nothing needs a gradient): the last
+    layer's norm + act, neck and conv_p are one op."""
+    from .heads import neck_rows
+
+    w = lambda n: p[f"{prefix}.{n}"]
+    P, F, L = N + M, form.feat_dim, form.num_layers
+    gn = lambda i: (w(f"layers.{3 * i + 1}.weight"), w(f"layers.{3 * i + 1}.bias")) if form.norm else (None, None)
+    W0g, W0b = T.split_cols(w("layers.0.weight").reshape(F, 1088), 1024)     # global half (a view) | point half
+    bias0 = T.linear(g, W0g, w("layers.0.bias"))                              # [2B,F]: global half + conv bias
+    y = T.linear_cloudbias(pf_obj, W0b, bias0, B, N, M)
+    rd = w("neck.0.weight").shape[0]
+    a = None
+    for i in range(L):
+        if i:
+            y = T.linear(a, w(f"layers.{3 * i}.weight"), w(f"layers.{3 * i}.bias"))
+        if fused_tail and i == L - 1:
+            return T.gn_points_act_neck_wsum(y, *gn(i), w("neck.0.weight"), w("neck.0.bias"), w("conv_p.weight"),
+                                             p.get(f"{prefix}.conv_p.bias"), B, P, form.groups, form.act, form.norm)
+        a = T.gn_points_act(y, *gn(i), B, P, form.groups, form.act, form.norm)
+    y3 = neck_rows(a, w("neck.0.weight"), w("neck.0.bias"))                  # [B*P,3] (columns >= rot_dim are zero)
+    return _first_cols(T.weighted_point_sum(y3, w("conv_p.weight"), p.get(f"{prefix}.conv_p.bias"), B, P), rd)
+
+
+def _ts_head(ts_feat, p, form):
+    """FC_TransSizeHead.forward (fc_trans_size_head.py:61-70) on however many layers ``form`` describes -> (dt, ds)."""
+    from .heads import SHIPPED_FORM
+
+    h = ts_feat
+    for i in range(form.num_layers):
+        h = T.linear(h, p[f"ts_head.linears.{3 * i}.weight"], p[f"ts_head.linears.{3 * i}.bias"])
+        if form == SHIPPED_FORM:
+            h = T.gn_rows_gelu(h, p[f"ts_head.linears.{3 * i + 1}.weight"], p[f"ts_head.linears.{3 * i + 1}.bias"])
+        else:
+            h = T.gn_rows_act(h, p.get(f"ts_head.linears.{3 * i + 1}.weight"), p.get(f"ts_head.linears.{3 * i + 1}.bias"),
+                              form.groups, form.act, form.norm)
+    return (T.linear(h, p["ts_head.fc_t.weight"], p["ts_head.fc_t.bias"]),
+            T.linear(h, p["ts_head.fc_s.weight"], p["ts_head.fc_s.bias"]))
+
+
+def heads_rows(p, opts, forms, g, pfmax, pf_obj, init_pose, init_scale, B, N, M, fused_tail=False):
+    """Both heads layer by layer from the encoder's outputs (g [2B,1024] pooled, pfmax [2B,64] max_n pointfeat, pf_obj
+    [B*(N+M),64] object-major) -> (rot [B, 2 rot_dim], dt, ds): the route of heads that are not the shipped form - training,
+    and with fused_tail the no-grad forward / refine."""
+    rot_form, ts_form = forms
+    feats = [g[:B], pfmax[:B]] + ([g[B:], pfmax[B:]] if opts.with_kps_feature else [])
+    if opts.with_init_scale:
+        feats.append(init_scale)
+    if opts.with_init_trans:
+        feats.append(init_pose[:, :3, 3])
+    dt, ds = _ts_head(torch.cat(feats, 1), p, ts_form)
+    rx, ry = (_rot_head_form(g, pf_obj, p, pre, B, N, M, rot_form, fused_tail) for pre in _ROT_PREFIX)
+    return torch.cat([rx, ry], 1), dt, ds
+
+
 _ROT_PREFIX = ("rot_head.rot_head_x", "rot_head.rot_head_y")
 
 
@@ -270,18 +329,27 @@ def _rot_heads_fused(g, pf, pf_obj, p, rt, B, N, M):
     return [_first_cols(o, p[f"{pre}.neck.0.weight"].shape[0]) for pre, o in zip(_ROT_PREFIX, outs)]
 
 
-def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_scales=None, rt=None):
+def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_scales=None, rt=None, forms=None):
     """p: {state_dict key: live parameter}.  Returns (pose [B,3,4], scale [B,3], aux dict) - autograd-connected.
-    ``rt``: the model's :class:`~catre_amd.runtime.HipRuntime`; with it the fp32 encoder forward takes the fused kernels."""
+    ``rt``: the model's :class:`~catre_amd.runtime.HipRuntime`; with it the fp32 encoder forward takes the fused kernels.
+    ``forms``: (rot head, ts head) ``heads.HeadForm`` - None or the shipped form keeps every route below as it is; a head of
+    another form runs layer by layer on the generic norm + activation ops."""
+    from .heads import SHIPPED_FORM
+
+    rot_form, ts_form = forms if forms is not None else (SHIPPED_FORM, SHIPPED_FORM)
+    rot_shipped = rot_form == SHIPPED_FORM
+    # (a runtime whose ts head alone has another form packs the encoder only: the rotation heads' fused forwards, which read
+    # the packed head image, are not taken then - the per-head ops are)
+    rot_packed = rot_shipped and not getattr(rt, "layered", False)
     B, N, M = x.shape[0], x.shape[2], tfd_kps.shape[2]
     hip.require_dev_f32(x, "x", (B, 3, N), contiguous=False)
     hip.require_dev_f32(tfd_kps, "tfd_kps", (B, 3, M), contiguous=False)
     # one decision, taken once: the fused fp32 rotation heads read pointfeat cloud-major (forward AND backward), so no
     # object-major copy is made for them
-    fused_rot = (rt is not None and T._amp() == 0 and bool(opts.feature_transform) and N + M == rt.N + rt.M
-                 and _rot_heads_shapes_ok_p(p, N, M))
+    fused_rot = (rot_packed and rt is not None and T._amp() == 0 and bool(opts.feature_transform)
+                 and N + M == rt.N + rt.M and _rot_heads_shapes_ok_p(p, N, M))
     # autocast: each head is one node (train_ops._RotHeadLP) that reads pointfeat cloud-major as well - no object-major copy
-    lp_cm = (rt is not None and T._amp() == 1 and T.knobs().fused_lp_rot and T.knobs().lp_rot_bf16_rows
+    lp_cm = (rot_shipped and rt is not None and T._amp() == 1 and T.knobs().fused_lp_rot and T.knobs().lp_rot_bf16_rows
              and bool(opts.feature_transform) and N + M == rt.N + rt.M and _rot_heads_shapes_ok_p(p, N, M))
     enc_frozen = (not x.requires_grad and not tfd_kps.requires_grad
                   and not any(v.requires_grad for k, v in p.items() if k.startswith("pcl_net.")))
@@ -326,16 +394,14 @@ def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_
     if opts.with_init_trans:
         feats.append(init_pose[:, :3, 3])
     ts_feat = torch.cat(feats, 1)                                             # [B, ts_in]
-    h = T.linear(ts_feat, p["ts_head.linears.0.weight"], p["ts_head.linears.0.bias"])
-    h = T.gn_rows_gelu(h, p["ts_head.linears.1.weight"], p["ts_head.linears.1.bias"])
-    h = T.linear(h, p["ts_head.linears.3.weight"], p["ts_head.linears.3.bias"])
-    h = T.gn_rows_gelu(h, p["ts_head.linears.4.weight"], p["ts_head.linears.4.bias"])
-    dt = T.linear(h, p["ts_head.fc_t.weight"], p["ts_head.fc_t.bias"])
-    ds = T.linear(h, p["ts_head.fc_s.weight"], p["ts_head.fc_s.bias"])
+    dt, ds = _ts_head(ts_feat, p, ts_form)
 
-    if fused_rot:
+    if not rot_shipped:
+        rx = _rot_head_form(gs[0], pf_obj, p, _ROT_PREFIX[0], B, N, M, rot_form)
+        ry = _rot_head_form(gs[1], pf_obj, p, _ROT_PREFIX[1], B, N, M, rot_form)
+    elif fused_rot:
         rx, ry = _rot_heads_fused(gs, pf, pf_obj, p, rt, B, N, M)
-    elif hub is not None and T._amp() == 2 and _rot_heads_shapes_ok(p, pf_obj, N, M):
+    elif rot_packed and hub is not None and T._amp() == 2 and _rot_heads_shapes_ok(p, pf_obj, N, M):
         rx, ry = _rot_heads_split(gs, pf, pf_obj, p, rt, B, N, M)
     elif lp_cm:
         rx, ry = _rot_heads_lp(gs, pf_obj, p, B, N, M, True)

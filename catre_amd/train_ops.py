@@ -1797,6 +1797,105 @@ def gn_rows_gelu(y, gamma, beta):
     return _GNRowsGelu.apply(y, gamma, beta)
 
 
+# ------------------------------------------------------------------------------------- norm + activation, any head form
+class _GNPointsAct(torch.autograd.Function):
+    """act(GroupNorm(G, C)(y)) - or act(y) with norm off - with statistics over the P points of each object (rows
+    object-major): the heads of any configured width / groups / activation (catre_op_gnp_act_*, csrc/catre_heads.h)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, B, P, G, act, norm):
+        lib = hip.load()
+        y = _c(y)
+        C = y.shape[1]
+        a = torch.empty_like(y)
+        stat = torch.empty(B, G, 2, dtype=torch.float32, device=y.device) if norm else None
+        hip.check(lib.catre_op_gnp_act_fwd(hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), hip.ptr(a), hip.ptr(stat), B, P, C,
+                                           int(G), int(act), int(norm), _st(y)), "catre_op_gnp_act_fwd")
+        ctx.save_for_backward(y, gamma, beta, stat)
+        ctx.dims = (B, P, int(G), int(act), int(norm))
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        y, gamma, beta, stat = ctx.saved_tensors
+        B, P, G, act, norm = ctx.dims
+        lib = hip.load()
+        da = _c(da)
+        C = y.shape[1]
+        dy = torch.empty_like(y)
+        dg, db, ws, nws = None, None, None, 0
+        if norm:
+            dg, db = torch.empty_like(gamma), torch.empty_like(beta)
+            ws = _ws(lib.catre_op_gnp_act_bwd_ws_bytes(B, P, C, G), y.device)
+            nws = ws.numel()
+        hip.check(lib.catre_op_gnp_act_bwd(hip.ptr(da), hip.ptr(y), hip.ptr(stat), hip.ptr(gamma), hip.ptr(beta), hip.ptr(dy),
+                                           hip.ptr(dg), hip.ptr(db), 0, hip.ptr(ws), nws, B, P, C, G, act, norm, _st(y)),
+                  "catre_op_gnp_act_bwd")
+        return dy, dg, db, None, None, None, None, None
+
+
+def gn_points_act(y, gamma, beta, B, P, G, act, norm=True):
+    """y [B*P, C] object-major -> act(GroupNorm(G, C)(y)) (norm=False: act(y); gamma / beta None).  act: ``hip.ACT_*``."""
+    return _GNPointsAct.apply(y, gamma, beta, B, P, G, act, bool(norm))
+
+
+class _GNRowsAct(torch.autograd.Function):
+    """act(GroupNorm(G, C)(y)) on FC rows [R, C] (statistics per row and group; ts head of any form)."""
+
+    @staticmethod
+    def forward(ctx, y, gamma, beta, G, act, norm):
+        lib = hip.load()
+        y = _c(y)
+        R, C = y.shape
+        a = torch.empty_like(y)
+        hip.check(lib.catre_op_gnr_act_fwd(hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), hip.ptr(a), R, C, int(G), int(act),
+                                           int(norm), _st(y)), "catre_op_gnr_act_fwd")
+        ctx.save_for_backward(y, gamma, beta)
+        ctx.dims = (int(G), int(act), int(norm))
+        return a
+
+    @staticmethod
+    def backward(ctx, da):
+        y, gamma, beta = ctx.saved_tensors
+        G, act, norm = ctx.dims
+        lib = hip.load()
+        da = _c(da)
+        R, C = y.shape
+        dy = torch.empty_like(y)
+        dg, db, ws, nws = None, None, None, 0
+        if norm:
+            dg, db = torch.empty_like(gamma), torch.empty_like(beta)
+            ws = _ws(lib.catre_op_gnr_act_bwd_ws_bytes(R, C), y.device)
+            nws = ws.numel()
+        hip.check(lib.catre_op_gnr_act_bwd(hip.ptr(da), hip.ptr(y), hip.ptr(gamma), hip.ptr(beta), hip.ptr(dy), hip.ptr(dg),
+                                           hip.ptr(db), 0, hip.ptr(ws), nws, R, C, G, act, norm, _st(y)),
+                  "catre_op_gnr_act_bwd")
+        return dy, dg, db, None, None, None
+
+
+def gn_rows_act(y, gamma, beta, G, act, norm=True):
+    return _GNRowsAct.apply(y, gamma, beta, G, act, bool(norm))
+
+
+def gn_points_act_neck_wsum(y, gamma, beta, wn, bn, wp, bp, B, P, G, act, norm=True):
+    """Inference tail of a RotHead of any form (no autograd): the last layer's norm + act, the neck (wn [rot_dim, C], bn) and
+    conv_p (wp [P], bp) in one op -> [B, rot_dim]; neither the [B*P, C] activation nor [B*P, 3] is stored."""
+    lib = hip.load()
+    y = _c(y.detach())
+    C = y.shape[1]
+    wn2 = _c(wn.detach().reshape(wn.shape[0], -1))
+    rd = wn2.shape[0]
+    wv = _c(wp.detach().reshape(-1))
+    keep = [t.detach() if t is not None else None for t in (gamma, beta, bn, bp)]
+    out = torch.empty(B, rd, dtype=torch.float32, device=y.device)
+    ws = _ws(lib.catre_op_gnp_act_neck_wsum_ws_bytes(B, P, int(G) if norm else 0), y.device)
+    hip.check(lib.catre_op_gnp_act_neck_wsum(hip.ptr(y), hip.ptr(keep[0]), hip.ptr(keep[1]), hip.ptr(wn2), hip.ptr(keep[2]),
+                                             hip.ptr(wv), hip.ptr(keep[3]), hip.ptr(out), hip.ptr(ws), ws.numel(), B, P, C,
+                                             int(G), rd, int(act), int(norm), _st(y)), "catre_op_gnp_act_neck_wsum")
+    del keep
+    return out
+
+
 # ------------------------------------------------------------------------------------------------- conv_p
 class _WSum(torch.autograd.Function):
     """out[b,:] = sum_p w[p] * y[b*P+p, :3] + bias  (the point-wise Conv1d(P,1,1) of RotHead)."""

@@ -511,6 +511,34 @@ int catre_op_pad_cols(const float* src, long stride_row, long stride_col, int ro
 int catre_op_gnr_gelu_fwd(const float* Y, const float* gamma, const float* beta, float* A, int R, void* stream);
 int catre_op_gnr_gelu_bwd(const float* dA, const float* Y, const float* gamma, const float* beta, float* dY,
                           float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes, int R, void* stream);
+/* Norm + activation stage of a head of any configured width (catre_amd/csrc/catre_heads.h): C channels (a multiple of 8,
+ * 8..1024), G GroupNorm groups (a divisor of C), act one of CATRE_ACT_*, norm 1 = GroupNorm(G, C) in front of the
+ * activation, 0 = the activation alone (gamma, beta, stat, dgamma, dbeta unused: NULL).  fp32, no atomics: bit-identical
+ * from run to run, and an object's rows do not depend on the batch around them.
+ *   gnp: rows [B*P, C] object-major, statistics over the P points of an object x the group's channels; forward writes A and
+ *        stat [B,G,2] = (mean, rstd) (needs P*C >= 2*G*ceil(P/64)); backward writes dY and dgamma, dbeta [C] (=|+=).
+ *   gnr: FC rows [R, C], statistics per (row, group).
+ *   neck_wsum: inference tail of a RotHead - the last layer's norm + act, the neck Conv1d(C -> rot_dim <= 3) (Wn
+ *        [rot_dim][C], bn [rot_dim] or NULL) and conv_p (wp [P], bp [1] or NULL): out [B][rot_dim] =
+ *        sum_p wp[p] y3[b,p,:] + bp.  Neither the [B*P, C] activation nor [B*P, 3] is stored. */
+enum { CATRE_ACT_NONE = 0, CATRE_ACT_RELU = 1, CATRE_ACT_LRELU = 2, CATRE_ACT_SILU = 3, CATRE_ACT_GELU = 4,
+       CATRE_ACT_MISH = 5 };
+int catre_op_gnp_act_fwd(const float* Y, const float* gamma, const float* beta, float* A, float* stat, int B, int P, int C,
+                         int G, int act, int norm, void* stream);
+size_t catre_op_gnp_act_bwd_ws_bytes(int B, int P, int C, int G);
+int catre_op_gnp_act_bwd(const float* dA, const float* Y, const float* stat, const float* gamma, const float* beta, float* dY,
+                         float* dgamma, float* dbeta, int accumulate, void* ws, size_t ws_bytes, int B, int P, int C, int G,
+                         int act, int norm, void* stream);
+int catre_op_gnr_act_fwd(const float* Y, const float* gamma, const float* beta, float* A, int R, int C, int G, int act,
+                         int norm, void* stream);
+size_t catre_op_gnr_act_bwd_ws_bytes(int R, int C);
+int catre_op_gnr_act_bwd(const float* dA, const float* Y, const float* gamma, const float* beta, float* dY, float* dgamma,
+                         float* dbeta, int accumulate, void* ws, size_t ws_bytes, int R, int C, int G, int act, int norm,
+                         void* stream);
+size_t catre_op_gnp_act_neck_wsum_ws_bytes(int B, int P, int G);
+int catre_op_gnp_act_neck_wsum(const float* Y, const float* gamma, const float* beta, const float* Wn, const float* bn,
+                               const float* wp, const float* bp, float* out, void* ws, size_t ws_bytes, int B, int P, int C,
+                               int G, int rot_dim, int act, int norm, void* stream);
 int catre_op_wsum_fwd(const float* Y, const float* w, const float* bias, float* out, int B, int P, void* stream);
 int catre_op_wsum_bwd(const float* dout, const float* Y, const float* w, float* dY, float* dw, float* dbias,
                       int accumulate, void* ws, size_t ws_bytes, int B, int P, void* stream);
