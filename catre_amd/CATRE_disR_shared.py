@@ -265,8 +265,9 @@ def _maybe_add_gradient_clipping(cfg, optimizer):
 def _build_optimizer(cfg, params_lr_list):
     """``core/utils/solver_utils.build_optimizer_with_params`` (reference ``:75-87``): ``OPTIMIZER_CFG`` (a dict, or the
     string form the reference ``eval``s) names the optimizer and carries its keyword arguments; the shipped config's
-    Ranger is ``catre_amd.ranger.Ranger`` (one fused multi-tensor HIP step); ``torch.optim`` types get every
-    keyword; then ``maybe_add_gradient_clipping``."""
+    Ranger is ``catre_amd.ranger.Ranger`` (one fused multi-tensor HIP step); the reference's other
+    optimizer classes are the fused steps of ``catre_amd.optimizers``; ``torch.optim`` types get every keyword; then
+    ``maybe_add_gradient_clipping``."""
     ocfg = cfg.SOLVER.get("OPTIMIZER_CFG", "")
     if isinstance(ocfg, str):
         if ocfg == "":
@@ -275,16 +276,20 @@ def _build_optimizer(cfg, params_lr_list):
     ocfg = dict(ocfg)
     typ = ocfg.pop("type")
     groups = [dict(params=list(g["params"]), lr=g["lr"]) for g in params_lr_list]
+    from .optimizers import FUSED_OPTIMIZERS
+
     if typ == "Ranger":  # the shipped config (…_120e.py:49)
         from .ranger import Ranger
 
         opt = Ranger(groups, **ocfg)
+    elif typ in FUSED_OPTIMIZERS:  # the reference's own classes (solver_utils.py:30-72), each one fused HIP step
+        opt = FUSED_OPTIMIZERS[typ](groups, **ocfg)
     elif hasattr(torch.optim, typ):
         opt = getattr(torch.optim, typ)(groups, **ocfg)
     else:
-        # Ranger21 / Lamb / MADGRAD / NAdamW / AdaBelief / SGDP / AdamP / SGD_GC of solver_utils.py:30-72 are generic
-        # third-party optimizers outside the hot path
-        raise ValueError(f"Unknown optimizer name: {typ} (available: 'Ranger' and every torch.optim class)")
+        # Ranger21 (645 lines of schedule and norm-loss state) and Lamb (timm's) of solver_utils.py:30-72 are not built
+        raise ValueError(f"Unknown optimizer name: {typ} (available: 'Ranger', "
+                         + ", ".join(repr(n) for n in FUSED_OPTIMIZERS) + " and every torch.optim class)")
     return _maybe_add_gradient_clipping(cfg, opt)
 
 

@@ -1565,6 +1565,7 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 #include "catre_gram.h"
 #include "catre_small.h"
 #include "catre_train.h"
+#include "catre_optim.h"
 #include "catre_heads.h"
 #include "catre_aug.h"
 #include "catre_pcl.h"

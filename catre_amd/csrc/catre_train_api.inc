@@ -1420,6 +1420,52 @@ int catre_op_ranger_step(const void* tensors, int n_tensors, const void* chunks,
 }
 
 
+// f4, the reference's other optimizers: one fused step of optimizer `kind` (CATRE_OPTIM_*) over every parameter tensor
+// that has a gradient.  `tensors` = device array of n_tensors packed 112-byte records {p, g, state[4] (6 pointers), numel,
+// row_len, row_off, flags, f[12]} (catre_optim.h says what each kind keeps in state / flags / f); `chunks` as for
+// catre_op_ranger_step; `row_tensor[n_rows]` maps every row of a tensor with row_len > 0 to its tensor.  `phases` bit 0:
+// some tensor needs the reductions over the inputs, bit 1: some tensor needs the reductions over the update direction;
+// a phase nobody needs is not launched.  ws >= (5 * n_rows + 4 * n_tensors) floats.
+int catre_op_optim_step(int kind, const void* tensors, int n_tensors, const void* chunks, int n_chunks, const int* row_tensor,
+                        int n_rows, int phases, float* ws, size_t ws_bytes, int clean_grads, float grad_limit, void* stream) {
+  REQUIRE(tensors && chunks && n_tensors > 0 && n_chunks > 0 && n_rows >= 0 && ws && (n_rows == 0 || row_tensor));
+  REQUIRE(ws_bytes >= ((size_t)5 * n_rows + (size_t)4 * n_tensors) * sizeof(float));
+  if (kind < 0 || kind >= OPT_KINDS) return CATRE_ERR_UNSUPPORTED;
+  hipStream_t st = (hipStream_t)stream;
+  const OptimTensor* T = (const OptimTensor*)tensors;
+  const int2* ch = (const int2*)chunks;
+  float *rowA = ws, *rowB = ws + (size_t)4 * n_rows, *tens = ws + (size_t)5 * n_rows;
+  const bool proj = kind == OPT_ADAMP || kind == OPT_SGDP;
+  const bool p1 = (phases & 1) && n_rows > 0, p2 = (phases & 2) && n_rows > 0;
+  if (p1 && proj) {
+    hipLaunchKernelGGL(k_optim_rowstats, dim3(n_rows), dim3(64), 0, st, T, row_tensor, rowA, clean_grads, grad_limit);
+    hipLaunchKernelGGL(k_optim_decide, dim3(n_tensors), dim3(64), 0, st, T, rowA, tens);
+  } else if (p1) {
+    hipLaunchKernelGGL(k_optim_rowmean, dim3(n_rows), dim3(64), 0, st, T, row_tensor, rowA, clean_grads, grad_limit);
+  }
+#define OPT_ROWS(K) \
+  hipLaunchKernelGGL(k_optim_dir_rows<K>, dim3(n_rows), dim3(64), 0, st, T, row_tensor, rowA, rowB, tens, clean_grads, grad_limit)
+#define OPT_UPDATE(K) \
+  hipLaunchKernelGGL(k_optim_update<K>, dim3(n_chunks), dim3(256), 0, st, T, ch, rowA, rowB, tens, clean_grads, grad_limit)
+  if (p2 && kind == OPT_RANGER_ADABELIEF) OPT_ROWS(OPT_RANGER_ADABELIEF);
+  if (p2 && kind == OPT_ADAMP) OPT_ROWS(OPT_ADAMP);
+  if (p2 && kind == OPT_SGDP) OPT_ROWS(OPT_SGDP);
+  if (p2 && proj) hipLaunchKernelGGL(k_optim_tensor_sum, dim3(n_tensors), dim3(64), 0, st, T, rowB, tens);
+  switch (kind) {
+    case OPT_ADABELIEF: OPT_UPDATE(OPT_ADABELIEF); break;
+    case OPT_RANGER_ADABELIEF: OPT_UPDATE(OPT_RANGER_ADABELIEF); break;
+    case OPT_MADGRAD: OPT_UPDATE(OPT_MADGRAD); break;
+    case OPT_NADAMW: OPT_UPDATE(OPT_NADAMW); break;
+    case OPT_ADAMP: OPT_UPDATE(OPT_ADAMP); break;
+    case OPT_SGDP: OPT_UPDATE(OPT_SGDP); break;
+    default: OPT_UPDATE(OPT_SGD_GC); break;
+  }
+#undef OPT_ROWS
+#undef OPT_UPDATE
+  return check_launch();
+}
+
+
 // ---- training forward of the encoder on the fused kernels (k_stn3d / k_stnkd / k_trunk with SAVE): one launch per
 // block computes the pooled feature AND writes the activations the layer-wise backward reads (cloud-major point rows),
 // instead of one row GEMM per layer with every intermediate streamed through HBM twice.  N, M multiples of 64.

@@ -220,6 +220,7 @@ _SIGS = {
     "catre_train_rot_fwd": (_I, [_P] * 10 + [_SZ, _I, _I, _I, _I, _P]),
     "catre_op_ranger_step": (_I, [_P, _I, _P, _I, _P, _I, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float,
                                   ctypes.c_float, _I, ctypes.c_float, _P]),
+    "catre_op_optim_step": (_I, [_I, _P, _I, _P, _I, _P, _I, _I, _P, _SZ, _I, ctypes.c_float, _P]),
     "catre_aug_points": (_I, [_P] * 10 + [_I, _I, _P]),
     "catre_init_noise": (_I, [_P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _P, _P, ctypes.c_float, ctypes.c_float, _P, _I,
                               _P]),

@@ -669,6 +669,37 @@ int catre_op_ranger_step(const void* tensors, int n_tensors, const void* chunks,
                          int total_rows, float* rowmean_ws, double beta1, double beta2, float eps, float alpha,
                          int clean_grads, float grad_limit, void* stream);
 
+/* f4, the reference's other optimizers (core/utils/solver_utils.py:28-87): one fused multi-tensor step of
+ *   CATRE_OPTIM_ADABELIEF        lib/torch_utils/solver/AdaBelief.py:113-218
+ *   CATRE_OPTIM_RANGER_ADABELIEF lib/torch_utils/solver/ranger_adabelief.py:133-265
+ *   CATRE_OPTIM_MADGRAD          lib/torch_utils/solver/madgrad.py:72-175
+ *   CATRE_OPTIM_NADAMW           lib/torch_utils/solver/nadamw.py:58-134
+ *   CATRE_OPTIM_ADAMP            lib/torch_utils/solver/adamp.py:48-123
+ *   CATRE_OPTIM_SGDP             lib/torch_utils/solver/sgdp.py:50-113
+ *   CATRE_OPTIM_SGD_GC           lib/torch_utils/solver/sgd_gc.py:42-180 (SGD_GC and SGD_GCC: the host decides which
+ *                                tensors are centralized)
+ * with the train loop's grad nan_to_num folded in like catre_op_ranger_step.  `tensors`: device array of n_tensors
+ * 112-byte records {float* p; const float* g; float* state[4]; int numel, row_len, row_off, flags; float f[12];} -
+ * every hyper-parameter and every scalar term of the step (bias corrections, rectification, `1 - beta`, ...) is formed
+ * on the host in double like the reference and passed per tensor in f[] (catre_amd/csrc/catre_optim.h lists the slots
+ * and flags of each kind; catre_amd/optimizers.py fills them).  `chunks`: {int tensor, offset} pairs of 4096 elements;
+ * `row_tensor[n_rows]`: tensor of every row of the tensors with row_len > 0.  `phases`: bit 0 = run the reductions over
+ * the inputs (row means of the gradient / the projection's cosine similarities and its choice of view, made on the
+ * device), bit 1 = run the reductions over the update direction; the elementwise update always runs.  ws holds
+ * (5 * n_rows + 4 * n_tensors) floats.  Stream-ordered, no atomics, nothing copied back.
+ * CATRE_ERR_BAD_ARG on null pointers / bad sizes, CATRE_ERR_UNSUPPORTED on an unknown kind. */
+enum catre_optim_kind {
+  CATRE_OPTIM_ADABELIEF = 0,
+  CATRE_OPTIM_RANGER_ADABELIEF = 1,
+  CATRE_OPTIM_MADGRAD = 2,
+  CATRE_OPTIM_NADAMW = 3,
+  CATRE_OPTIM_ADAMP = 4,
+  CATRE_OPTIM_SGDP = 5,
+  CATRE_OPTIM_SGD_GC = 6
+};
+int catre_op_optim_step(int kind, const void* tensors, int n_tensors, const void* chunks, int n_chunks, const int* row_tensor,
+                        int n_rows, int phases, float* ws, size_t ws_bytes, int clean_grads, float grad_limit, void* stream);
+
 /* Build identification: "catre_hip gfx950 <version>" */
 const char* catre_version(void);
 
