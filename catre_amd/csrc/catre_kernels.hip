@@ -800,16 +800,42 @@ __global__ __launch_bounds__(512) void k_trunk(catre_points P, const float* __re
 #ifndef TRUNK4_PFB
 #define TRUNK4_PFB 1
 #endif
-template <bool SAVE = false>
-__global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __restrict__ trans3,
-                                                const float* __restrict__ trans64, const float* __restrict__ Wc1,
-                                                const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
-                                                const float* __restrict__ b2, const f32x4* __restrict__ wp3,
-                                                const float* __restrict__ b3, const f32x4* __restrict__ wp4,
-                                                const float* __restrict__ b4, float* __restrict__ pm,
-                                                float* __restrict__ pointfeat, int B, int N, int M,
-                                                unsigned long long* __restrict__ trace, TrainSave sv = TrainSave{}) {
-  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
+// conv4 + max-pool of k_trunk4 as a policy of trunk4_body: `prefetch` (first weight chunks + bias, requested behind conv3's
+// sweep), `sweep` (after the barrier that completes a3), `store`.  Trunk4Dense is the full fp32 sweep; catre_screen.h adds
+// the screened form of the same layer.
+template <bool SAVE>
+struct Trunk4Dense {
+  GemmPipe<8, 2, true, true, 64, TRUNK4_PFD, TRUNK4_PFB> g4;
+  float bl4[8];
+  f32x16 acc4[8][2];
+  __device__ __forceinline__ void prefetch(const f32x4* __restrict__ wp4, const float* __restrict__ b4, int mb0, int lane) {
+    g4.prefetch(wp4 + ((size_t)mb0 * 64) * 64 + lane, 64 * 64);
+    load_bias_lane<8>(bl4, b4, mb0 * 32, lane);
+  }
+  __device__ __forceinline__ void sweep(const float* a3, float*, int, int lane) {
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb) acc4[mb][0] = acc4[mb][1] = zero16();
+    g4.run(acc4, a3, 512, lane);
+  }
+  __device__ __forceinline__ void store(const float*, float*, float* __restrict__ pm, int tile, int mb0, int,
+                                        int trow0, const TrainSave& sv, int lane) {
+    if constexpr (SAVE) {
+      argmax_tile_store<8, 2>(acc4, sv.pmax + (size_t)tile * 1024, sv.pidx + (size_t)tile * 1024, mb0 * 32, bl4, trow0, lane);
+    } else {
+      max_tile_store_pre<8, 2>(acc4, pm + (size_t)tile * PMW, mb0 * 32, bl4, false, lane);
+    }
+  }
+};
+
+template <bool SAVE, class Tail>
+__device__ __forceinline__ void trunk4_body(float* smem, catre_points P, const float* __restrict__ trans3,
+                                            const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                            const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
+                                            const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                            const float* __restrict__ b3, const f32x4* __restrict__ wp4,
+                                            const float* __restrict__ b4, float* __restrict__ pm,
+                                            float* __restrict__ pointfeat, int B, int N, int M,
+                                            unsigned long long* __restrict__ trace, const TrainSave& sv, Tail& tl) {
 #define TRUNK_STAMP(i)                                                                     \
   do {                                                                                     \
     if (CATRE_TRACE_ON && trace && lane == 0) trace[((size_t)tile * 8 + wave) * 8 + (i)] = __builtin_readcyclecounter(); \
@@ -914,8 +940,6 @@ __global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __r
   if (SAVE) save_tile_rows<128, 256, true>(a2, 128, sv.s3 + trow0 * 128, tid);
   // conv4 512->1024: wave owns 8 m-blocks (channels [wave*256, +256)); first weight chunks + bias requested now
   const int mb0 = wave * 8;
-  GemmPipe<8, 2, true, true, 64, TRUNK4_PFD, TRUNK4_PFB> g4;
-  float bl4[8];
   {
     f32x16 acc3[4][2];
 #pragma unroll
@@ -923,8 +947,7 @@ __global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __r
     g3.run(acc3, a2, 128, lane);
     // conv4's first weight chunks + bias are requested behind conv3's sweep: the L2 round trip hides behind the epilogue
     // and the barrier, and the 64 registers they land in are not live during the sweep
-    g4.prefetch(wp4 + ((size_t)mb0 * 64) * 64 + lane, 64 * 64);
-    load_bias_lane<8>(bl4, b4, mb0 * 32, lane);
+    tl.prefetch(wp4, b4, mb0, lane);
     __builtin_amdgcn_sched_barrier(0);
     store_tile_lds_pre<4, 2, true, true>(acc3, a3, 512, wave * 128, bv3, lane);
     TRUNK_STAMP(4);
@@ -941,19 +964,25 @@ __global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __r
     if (tid < 64) pm[(size_t)tile * PMW + 1024 + tid] = pf_max;
   }
   if (SAVE) save_tile_rows<512, 256, true>(a3, 512, sv.s4 + trow0 * 512, tid);
-  f32x16 acc4[8][2];
-#pragma unroll
-  for (int mb = 0; mb < 8; ++mb) acc4[mb][0] = acc4[mb][1] = zero16();
-  g4.run(acc4, a3, 512, lane);
+  tl.sweep(a3, a2, tid, lane);  // (a2 is dead since the barrier: scratch of the screened form)
   TRUNK_STAMP(6);
-  if constexpr (SAVE) {
-    argmax_tile_store<8, 2>(acc4, sv.pmax + (size_t)tile * 1024, sv.pidx + (size_t)tile * 1024, mb0 * 32, bl4, (int)trow0,
-                            lane);
-  } else {
-    max_tile_store_pre<8, 2>(acc4, pm + (size_t)tile * PMW, mb0 * 32, bl4, false, lane);
-  }
+  tl.store(a3, a2, pm, tile, mb0, ti.valid, (int)trow0, sv, lane);
   TRUNK_STAMP(7);
 #undef TRUNK_STAMP
+}
+
+template <bool SAVE = false>
+__global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __restrict__ trans3,
+                                                const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
+                                                const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                                const float* __restrict__ b3, const f32x4* __restrict__ wp4,
+                                                const float* __restrict__ b4, float* __restrict__ pm,
+                                                float* __restrict__ pointfeat, int B, int N, int M,
+                                                unsigned long long* __restrict__ trace, TrainSave sv = TrainSave{}) {
+  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
+  Trunk4Dense<SAVE> tl;
+  trunk4_body<SAVE>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace, sv, tl);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1533,6 +1562,7 @@ __global__ __launch_bounds__(256) void k_colmax(const float* __restrict__ x, flo
 
 #include "catre_bf16.h"
 #include "catre_split.h"
+#include "catre_screen.h"
 
 // every bf16 (or hi + lo split) fragment pack of a weight image in ONE launch (k_pack_frag_multi's job table; the
 // per-element arithmetic is k_pack_frag_bf's / k_pack_frag_split's): a training step re-packs the image after every
@@ -1587,6 +1617,9 @@ struct PackLayout {
   size_t sp_stn_c2, sp_stn_c3, sp_fstn_c1, sp_fstn_c2, sp_fstn_c3, sp_c3, sp_c4, sp_rot_l0[2], sp_rot_l1[2];
   // fp16 fragment packs of the bf16 packs' matrices, same layout (CATRE_PACK_F16, CATRE_DTYPE_F16), offsets in floats
   size_t f16_stn_c2, f16_stn_c3, f16_fstn_c1, f16_fstn_c2, f16_fstn_c3, f16_c2, f16_c3, f16_c4, f16_rot_l0[2], f16_rot_l1[2];
+  // screened max-pool of the fp32 path (catre_screen.h), part of the fp32 encoder pack: hi + lo bf16 fragments of conv4 and
+  // its weight-row norms
+  size_t scr_c4, scr_nw4;
 };
 
 PackLayout pack_layout(int ts_in) {
@@ -1645,6 +1678,8 @@ PackLayout pack_layout(int ts_in) {
     L.f16_rot_l0[h] = take(256 * 64 / 2);
     L.f16_rot_l1[h] = take(256 * 256 / 2);
   }
+  L.scr_c4 = take(1024 * 512);
+  L.scr_nw4 = take(1024);
   // everything above is independent of ts_in (the stage entry points rely on that)
   L.ts_w0t = take((size_t)ts_in * 256);
   L.ts_w1t = take(256 * 256);
@@ -1789,9 +1824,13 @@ static int bf_pair_min() {
 // Which kernel FORM a full grid takes where more than one exists (all forms of a stage give the same bits; the switches
 // exist for A/B measurements and for tests that compare the forms in one process).  Defaults: the encoder forms on,
 // k_rot_l1w OFF (it measured 8 % slower than k_rot_l1<1>: profiles/r06_rotw_phases.txt), k_fc_tail OFF (one object:
-// 0.643 vs 0.620 ms per K = 4 refine, profiles/r06_fc_tail_ab.jsonl); the environment (CATRE_TRUNK4 / CATRE_STN4 /
-// CATRE_STN_PAIR = 0, CATRE_ROTW / CATRE_FC_TAIL = 1) sets the process default once, catre_form_switch changes it at run time.
-enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16 };
+// 0.643 vs 0.620 ms per K = 4 refine, profiles/r06_fc_tail_ab.jsonl), the screened conv4 max-pool k_trunk4s ON (30.7 vs 34.0 ms
+// per K = 4 refine at B = 256, profiles/screen_ab.jsonl); the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR /
+// CATRE_SCREEN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1) sets the process default once, catre_form_switch changes it at run time.
+enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32 };
+#ifndef CATRE_SCREEN_DEFAULT
+#define CATRE_SCREEN_DEFAULT true
+#endif
 static std::atomic<int> g_forms{-1};
 static int forms() {
   int v = g_forms.load(std::memory_order_relaxed);
@@ -1802,7 +1841,7 @@ static int forms() {
     };
     v = (on("CATRE_TRUNK4") ? FORM_TRUNK4 : 0) | (on("CATRE_STN4") ? FORM_STN4 : 0) |
         (on("CATRE_STN_PAIR") ? FORM_STN_PAIR : 0) | (on("CATRE_ROTW", false) ? FORM_ROTW : 0) |
-        (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0);
+        (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0);
     g_forms.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -1812,6 +1851,7 @@ inline int stn_pairs(int B, int N, int M) { return B * (((N + TP - 1) / TP + 1) 
 static bool stn_pair_on() { return forms() & FORM_STN_PAIR; }  // off: one tile per workgroup
 static bool stn4_on() { return forms() & FORM_STN4; }
 static bool fc_tail_on() { return forms() & FORM_FC_TAIL; }  // B <= 8: an FC tail as one launch (k_fc_tail); off (default: the fused form measured SLOWER, profiles/r06_fc_tail_ab.jsonl): three k_linear launches
+static bool screen_on() { return forms() & FORM_SCREEN; }  // fp32 full grids: conv4's max-pool screened on the bf16 pipe (k_trunk4s)
 static bool rotw_on() { return forms() & FORM_ROTW; }  // rotation heads, one wave per SIMD (k_rot_l1w); off (default): k_rot_l1<1>
 
 // The measurement hooks are the library's only process-global mutable state.  They are fenced: compiled out entirely
@@ -1911,7 +1951,7 @@ void launch_stnkd(const catre_points* pts, const float* trans3, const float* con
 
 void launch_trunk(const catre_points* pts, const float* trans3, const float* trans64, const float* const* prm,
                   const float* packed, float* pointfeat, float* ws, const WsLayout& W, int B, int N, int M, bool split,
-                  hipStream_t st) {
+                  hipStream_t st, float* probe_s = nullptr, float* probe_eps = nullptr) {
   const PackLayout L = pack_layout(1);
   const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
   ProfScope ps(CATRE_K_TRUNK, st);
@@ -1923,6 +1963,11 @@ void launch_trunk(const catre_points* pts, const float* trans3, const float* tra
                      ws + W.pm, pointfeat, B, N, M, g_trunk_trace)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
+  } else if (row_split8(tiles) == 1 && trunk4_on() && (screen_on() || probe_s)) {
+    hipLaunchKernelGGL(k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
+                       prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
+                       prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
+                       g_trunk_trace, ScreenArgs{pkb(packed, L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps});
   } else if (row_split8(tiles) == 1 && trunk4_on()) {
     hipLaunchKernelGGL(k_trunk4<false>, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
                        prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
@@ -2087,6 +2132,12 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
   frag(prm[CATRE_P_CONV2_W], 64, 0, 128, 64, L.c2);
   frag(prm[CATRE_P_CONV3_W], 128, 0, 512, 128, L.c3);
   frag(prm[CATRE_P_CONV4_W], 512, 0, 1024, 512, L.c4);
+  if (prm[CATRE_P_CONV4_W]) {  // the screen's operands of conv4 (k_trunk4s)
+    frag_sp(prm[CATRE_P_CONV4_W], 512, 1024, 512, L.scr_c4);
+    flush_lp(LP_SPLIT);
+    hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
+                       packed + L.scr_nw4);
+  }
   }
   for (int h = 0; h < 2 && head32; ++h) {
     const int base = h ? CATRE_P_ROTY_L0_W : CATRE_P_ROTX_L0_W;
@@ -2167,6 +2218,21 @@ int catre_trunk(const catre_points* pts, const float* trans3, const float* trans
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
   launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st);
+  hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
+  return check_launch();
+}
+
+int catre_trunk_screen_probe(const catre_points* pts, const float* trans3, const float* trans64, const float* const* prm,
+                             const float* packed, float* screen, float* eps, float* gfeat, float* pointfeat, void* workspace,
+                             size_t ws_bytes, int B, int N, int M, void* stream) {
+  REQUIRE(pts && trans3 && prm && packed && screen && eps && gfeat && pointfeat && workspace && dims_ok1(B, N, M));
+  const WsLayout W = ws_layout(B, N, M);
+  if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
+  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
+  if (row_split8(tiles) != 1 || !trunk4_on()) return CATRE_ERR_UNSUPPORTED;  // the screened form exists for full grids only
+  float* ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st, screen, eps);
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
   return check_launch();
 }
@@ -2686,7 +2752,7 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 4) return -1;
+  if (id < 0 || id > 5) return -1;
   const int bit = 1 << id;
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);
@@ -2714,6 +2780,22 @@ int catre_stream_capture_id(void* stream, unsigned long long* id_out) {
   if (hipStreamGetCaptureInfo((hipStream_t)stream, &status, &id) != hipSuccess) return CATRE_ERR_LAUNCH;
   *id_out = status == hipStreamCaptureStatusActive ? id : 0ull;
   return CATRE_OK;
+}
+
+int catre_debug_screen_counts(unsigned long long* out64, int reset) {
+#ifdef CATRE_DEBUG_TRACE
+  REQUIRE(out64);
+  if (hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_screen_cnt), 64 * sizeof(unsigned long long)) != hipSuccess) return CATRE_ERR_LAUNCH;
+  if (reset) {
+    const unsigned long long z[64] = {};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_screen_cnt), z, sizeof(z)) != hipSuccess) return CATRE_ERR_LAUNCH;
+  }
+  return CATRE_OK;
+#else
+  (void)out64;
+  (void)reset;
+  return CATRE_ERR_UNSUPPORTED;
+#endif
 }
 
 int catre_debug_trunk_trace(void* device_buffer) {

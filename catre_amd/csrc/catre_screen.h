@@ -1,0 +1,448 @@
+// catre_screen.h - exact max-pool of a 1x1-conv layer without computing every output in fp32:
+// screen every (channel, point) with the split-bf16 product (catre_split.h, 3/16 of the fp32 MFMA issue), bound its error
+// rigorously, and recompute in the fp32 MFMA's own fmaf order only the points the bound cannot rule out.
+// Included by catre_kernels.hip after catre_split.h.
+//
+// The bound
+// ---------
+// Pooled layer y_c(p) = sum_{k < K} w_ck a_k(p), evaluated today by v_mfma_f32_32x32x2_f32 as an fmaf chain (call the
+// result Y).  The screen value S is  sum_k (wh ah + wh al + wl ah)  accumulated in fp32 by v_mfma_f32_32x32x16_bf16, with
+// x = xh + xl + rho, xh = bf16(x), xl = bf16(x - xh).  Write u = 2^-24, A = sum_k |w_ck| |a_k(p)| <= ||w_c||_2 ||a(p)||_2.
+//   * representation:   |rho| <= 2^-9 2^-9 |x| = 2^-18 |x| for w and for a            -> 2 * 2^-18 A
+//   * dropped wl al:    |wl| <= 2^-9 |w| (1 + 2^-9), same for a                        -> 2^-18 A (1 + 2^-8)
+//   * screen accumulation: 3K products enter fp32 sums; allowing every add to TRUNCATE (2u relative to a partial sum that
+//     never exceeds A (1 + small)), and counting the 17 addends of each of the 3 K/16 MFMAs:  3.19 K 2u A = 3.19 K 2^-23 A
+//   * the fp32 chain Y itself: K fused multiply-adds, round to nearest                -> K u A = 0.5 K 2^-23 A
+//   * second-order terms ((1 + 2u)^{3.2K} - 1 - 3.2K 2u etc.) are < 2e-4 of the first-order ones for K <= 512.
+// Together |Y - S| <= (3 * 2^-18 + 3.7 K 2^-23) A; the code uses
+//     gamma_K = 3 * 2^-18 + 4 K 2^-23
+// which leaves 8 % of the accumulation term for the second-order terms and the 2^-26 above.
+//   * flushed denormals: a bf16 piece, a product or a partial sum below 2^-126 may be flushed to zero on the matrix pipe.
+//     Per operand piece that is <= 2^-125 (hi and lo), so sum_k (|w_k| + |a_k|) 2^-125 <= sqrt(K) 2^-125 (||w|| + ||a||),
+//     plus <= 7 K 2^-126 for products / partial sums of the three screen products and of the chain.  The code adds
+//     delta_K (||w_c|| + ||a(p)|| + 1),  delta_K = K 2^-122, which covers both.
+// eps_c(p) = (gamma_K nw_c na_p + delta_K (nw_c + na_p + 1)) * infl with
+//   nw_c >= ||w_c||_2 : k_screen_wnorm at pack time, summed in double, rounded up
+//   na_p >= ||a(p)||_2: from the fp32 LDS image; fp32 sum of squares (relative error <= K u, a square below 2^-126 may be
+//                       lost: <= sqrt(K) 2^-63 absolute), so na_p = sqrt(sum) (1 + 2^-12) + 2^-58
+//   infl = 1 + 2^-22 / gamma_K + 2^-20: the selection below evaluates fl(S - eps) and fl(S + eps); each rounding is at most
+//         u (|S| + eps), and eps >= gamma_K |y| gives |S| <= eps (1 / gamma_K + 1), so the inflation covers them (and the
+//         three roundings of eps itself).
+// Not covered: Inf / NaN activations (the dense form gives Inf / NaN there; this form may give a finite other value).
+//
+// Selection: per (tile, channel) L = max_p fl(S - eps); the candidates are the points with fl(S + eps) >= L.  The true
+// maximum's point always is one (Y_max <= S + eps there, and L <= max_p Y).  Points of a ragged tile beyond `valid` are
+// copies of the last valid point (load_point clamps) - identical S and eps - and are dropped from the candidate set.
+// The tile maximum is fmaxf over the candidates' replayed Y, then bias exactly as max_tile_store_pre.
+//
+// Replay: GemmPipe::run feeds output (channel c, point p) the products in the order  kc = 0 .. K/8-1, s = 0 .. 3:
+// k = 8 kc + s, then k = 8 kc + 4 + s, starting from 0 - as fmaf (profiles/experiments/screen_mfma_chain.md).
+#pragma once
+
+template <int K>
+struct ScreenBound {
+  static constexpr float gamma = 3.f * 0x1p-18f + 4.f * K * 0x1p-23f;
+  static constexpr float delta = K * 0x1p-122f;
+  static constexpr float infl = 1.f + 0x1p-22f / gamma + 0x1p-20f;
+};
+// eps = fmaf(e1, na, e0) with the per-channel pair (e1, e0)
+template <int K>
+__device__ __forceinline__ void screen_eps_coef(float nw, float& e1, float& e0) {
+  e1 = fmaf(ScreenBound<K>::gamma, nw, ScreenBound<K>::delta) * ScreenBound<K>::infl;
+  e0 = ScreenBound<K>::delta * (nw + 1.f) * ScreenBound<K>::infl;
+}
+
+// nw[row] >= ||W[row][0:K]||_2: one wave per row, double accumulation, rounded up
+__global__ __launch_bounds__(256) void k_screen_wnorm(const float* __restrict__ W, int ld, int rows, int K,
+                                                      float* __restrict__ nw) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  double s = 0.0;
+  for (int k = lane; k < K; k += 64) {
+    const double w = W[(size_t)row * ld + k];
+    s += w * w;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) nw[row] = (float)sqrt(s) * (1.f + 0x1p-21f);
+}
+
+struct ScreenArgs {
+  const u32x4* wps;   // hi fragments of the layer ([mb][K/16][lane]), lo fragments rows*K/8 further (k_pack_frag_lp_multi<true>)
+  const float* nw;    // [rows] weight-row norms (k_screen_wnorm)
+  float* probe_s;     // tests only (catre_trunk_screen_probe): [tile][channel][point] screen value and bound, or NULL
+  float* probe_eps;
+};
+
+#ifdef CATRE_DEBUG_TRACE
+// diagnostic build: [0..31] candidates per (tile, channel) (31: >= 31), [32..47] trips per (wave, tile, m-block)
+// (47: >= 15), [48] (wave, tile) units with an m-block of more than SCREEN_CMAX trips, [49] all units
+__device__ unsigned long long g_screen_cnt[64];
+#endif
+
+#define SCREEN_CMAX 4  // replay chains a lane carries at once; an m-block that needs more trips takes further rounds
+
+// ||a(p)||_2 (rounded up) of the 64 rows of a swizzled [64][C] fp32 LDS image -> na[64]; NT threads, NT/64 per row
+template <int C, int NT>
+__device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, float* __restrict__ na, int tid) {
+  constexpr int PER = NT / 64, CH = C / 4 / PER;  // chunks of 4 floats per thread
+  static_assert(CH % 16 == 0, "a thread's chunks are whole swizzle groups");
+  const int row = tid / PER, part = tid % PER;
+  const float* r = img + row * C + part * CH * 4;
+  float s = 0.f;
+#pragma unroll 8
+  for (int j = 0; j < CH; ++j) {  // physical chunk j ^ (row & 15): the 16 rows of a lane group hit 16 distinct bank slots
+    const f32x4 v = *reinterpret_cast<const f32x4*>(r + ((j ^ (row & 15)) << 2));
+    s = fmaf(v[0], v[0], s);
+    s = fmaf(v[1], v[1], s);
+    s = fmaf(v[2], v[2], s);
+    s = fmaf(v[3], v[3], s);
+  }
+#pragma unroll
+  for (int o = 1; o < PER; o <<= 1) s += __shfl_xor(s, o);
+  if (part == 0) na[row] = fmaf(sqrtf(s), 1.f + 0x1p-12f, 0x1p-58f);
+}
+
+// The screen sweep of an MB8 x NB2 wave tile over K = 512: split-bf16 A fragments from the pack, B fragments split in
+// registers from the fp32 swizzled LDS image [64][512] (there is no LDS left for hi / lo images beside it).
+// The weight ring works on HALF chunks (4 m-blocks x K=16: 24 MFMAs = 768 cycles), PFD of them in flight.
+template <int PFD>
+struct ScreenPipe8 {
+  static constexpr int NKC = 32, NT = 2 * NKC, RA = PFD + 1, LO = 1024 * 512 / 8;
+  u32x4 ah[RA][4], al[RA][4];
+  const u32x4* wp;
+
+  __device__ __forceinline__ void issue_a(int t) {
+    const int kc = t >> 1, half = t & 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) {
+      ah[t % RA][m] = wp[((half * 4 + m) * NKC + kc) * 64];
+      al[t % RA][m] = wp[LO + ((half * 4 + m) * NKC + kc) * 64];
+    }
+  }
+  __device__ __forceinline__ void prefetch(const u32x4* __restrict__ wp_) {
+    wp = wp_;
+    // the caller's previous layer is still in its epilogue: PFD - 1 slots now (PFD = 2: one slot, 8 u32x4 = 32
+    // registers; the whole ring of RA = 3 slots is 96), the last one at the head of run()
+#pragma unroll
+    for (int d = 0; d < PFD - 1; ++d) issue_a(d);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void run(f32x16 (&acc)[8][2], const float* x, int lane) {
+    const int n = lane & 31, h = lane >> 5, sw = lane & 15;
+    const float* xrow = x + n * 512;
+    // k-slot order of the bf16 fragments: element e of lane half h is k = 16 kc + 8 (e >> 2) + 4 h + (e & 3), i.e. the fp32
+    // chunks 4 kc + h and 4 kc + 2 + h of the row; the XOR touches the low four chunk bits only (see GemmPipe::run)
+    const float* xlow[4][2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) xlow[q][j] = xrow + (((4 * q + 2 * j + h) ^ sw) << 2);
+    f32x4 braw[2][2];
+    u32x4 bh[2][2], bl[2][2];  // [chunk parity][nb]
+    auto issue_b = [&](int kc) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          braw[nb][j] = *reinterpret_cast<const f32x4*>(xlow[kc & 3][j] + (kc >> 2) * 64 + nb * 32 * 512);
+    };
+    auto split_b = [&](int kc) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        const float v[8] = {braw[nb][0][0], braw[nb][0][1], braw[nb][0][2], braw[nb][0][3],
+                            braw[nb][1][0], braw[nb][1][1], braw[nb][1][2], braw[nb][1][3]};
+        split_bf8(v, bh[kc & 1][nb], bl[kc & 1][nb]);
+      }
+    };
+    issue_a(PFD - 1);
+    issue_b(0);
+    split_b(0);
+    issue_b(1);
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int t = 2 * kc + half;
+        if (t + PFD < NT) issue_a(t + PFD);
+        __builtin_amdgcn_sched_barrier(0);
+        // second half: the split of the NEXT chunk's B fragments (~50 VALU ops) rides between this half's MFMAs - issued in
+        // one block ahead of them it would leave the matrix pipe idle for its whole length
+        if (half == 1 && kc + 1 < NKC) split_b(kc + 1);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            f32x16& c = acc[half * 4 + m][nb];
+            c = mfma_bf(bh[kc & 1][nb], al[t % RA][m], c);
+            c = mfma_bf(bl[kc & 1][nb], ah[t % RA][m], c);
+            c = mfma_bf(bh[kc & 1][nb], ah[t % RA][m], c);
+          }
+        if (half == 1 && kc + 1 < NKC) {
+#pragma unroll
+          for (int g = 0; g < 24; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // up to three VALU ops behind it
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (half == 1 && kc + 2 < NKC) issue_b(kc + 2);  // braw is free again
+      }
+    }
+  }
+};
+
+// 16 weight quads = 8 fp32 chunks kc of one channel row: [2 kc] = k 8kc .. 8kc+3, [2 kc + 1] = k 8kc+4 .. 8kc+7
+__device__ __forceinline__ void screen_load_w(f32x4 (&wb)[16], const f32x4* __restrict__ w) {
+#pragma unroll
+  for (int kc = 0; kc < 8; ++kc) {
+    wb[2 * kc] = w[kc * 64];
+    wb[2 * kc + 1] = w[kc * 64 + 32];
+  }
+}
+
+// Replay of T outputs of ONE channel (this lane's) at points p[0..T): the fmaf chain of GemmPipe::run over K = 8 NKC8 * 8.
+//   w    : fp32 fragment image of the channel's m-block, + (lane & 31)   (float4 (kc * 64 + 32 h') = k 8kc + 4h' ..)
+//   wb   : wb[0] holds the first 8 chunks on entry (requested by the previous call); on exit it holds those of `wnext`
+//   x    : swizzled fp32 LDS image [64][ld]
+// returns the maximum of the T results
+template <int T, int NKC8>
+__device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, const f32x4* __restrict__ wnext,
+                                               f32x4 (&wb)[2][16], const float* x, int ld, const int (&p)[SCREEN_CMAX]) {
+  static_assert(NKC8 % 2 == 0 && (T == 1 || T == 2 || T == 4), "two blocks of 8 chunks per trip");
+  // LDS rows are read one STAGE (SB chunks of every chain: 8 float4) ahead of their use, the weights one block of 8
+  // chunks ahead; both pinned where they are issued - left alone the compiler hoists a whole block's reads (256 registers)
+  constexpr int SB = 4 / T, NS = 8 / SB;
+  float y[T];
+  const float* row[T];
+  int key[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    y[j] = 0.f;
+    row[j] = x + p[j] * ld;
+    key[j] = p[j] & 15;
+  }
+  f32x4 ab[2][SB][T][2];
+  auto load_stage = [&](int buf, int b8, int st) {  // chunks kc = 8 b8 + SB st .. + SB
+#pragma unroll
+    for (int i = 0; i < SB; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+          ab[buf][i][j][e] =
+              *reinterpret_cast<const f32x4*>(row[j] + b8 * 64 + (((2 * (SB * st + i) + e) ^ key[j]) << 2));
+  };
+  auto block = [&](const f32x4 (&wv)[16], int b8, int b8next) {
+#pragma unroll
+    for (int st = 0; st < NS; ++st) {
+      if (st + 1 < NS)
+        load_stage((st + 1) & 1, b8, st + 1);
+      else
+        load_stage(0, b8next, 0);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < SB; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            y[j] = fmaf(wv[2 * (SB * st + i)][s], ab[st & 1][i][j][0][s], y[j]);
+            y[j] = fmaf(wv[2 * (SB * st + i) + 1][s], ab[st & 1][i][j][1][s], y[j]);
+          }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  load_stage(0, 0, 0);
+#pragma unroll 1
+  for (int it = 0; it < NKC8 / 2; ++it) {
+    screen_load_w(wb[1], w + (2 * it + 1) * 8 * 64);
+    __builtin_amdgcn_sched_barrier(0);
+    block(wb[0], 2 * it, 2 * it + 1);
+    screen_load_w(wb[0], it + 1 < NKC8 / 2 ? w + (2 * it + 2) * 8 * 64 : wnext);
+    __builtin_amdgcn_sched_barrier(0);
+    block(wb[1], 2 * it + 1, (2 * it + 2) % NKC8);  // (after the last block: a read of block 0 that nothing uses)
+  }
+  float m = y[0];
+#pragma unroll
+  for (int j = 1; j < T; ++j) m = fmaxf(m, y[j]);
+  return m;
+}
+
+// Epilogue of a screened "swapped" MB x 2 wave tile: select, replay, store.  acc holds the screen values S of channels
+// ch0 + 32 mb + (lane & 31) at points 32 nb + (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
+//   wf  : fp32 fragment image of the layer, at the wave's first m-block, + (lane & 31);  K / 64 blocks of 8 chunks
+//   na  : LDS, [64] row norms (screen_row_norms); x: the fp32 image the screen read
+//   sets: LDS, this wave's [MB][64] candidate sets - the replay loop over the m-blocks is NOT unrolled (its body is the
+//         three replay forms: unrolled MB times it would not fit the instruction cache), so what the selection leaves per
+//         m-block goes through LDS instead of a register array
+template <int MB, int K>
+__device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
+                                                    const float* __restrict__ nw, const float* na, const float* x,
+                                                    unsigned long long* sets, float* __restrict__ out,
+                                                    const float* __restrict__ bias, int ch0, bool relu, int valid, int tile,
+                                                    const ScreenArgs& sc, int lane) {
+  constexpr int NKC8 = K / 64;
+  const int n = lane & 31, h = lane >> 5;
+  const int partner = (lane ^ 32) << 2;  // ds_bpermute address of the channel's other half-wave lane
+  auto swap32 = [&](auto v) { return __builtin_bit_cast(decltype(v), __builtin_amdgcn_ds_bpermute(partner, __builtin_bit_cast(int, v))); };
+  // first weight chunks of the replay: requested before the selection arithmetic
+  f32x4 wb[2][16];
+  screen_load_w(wb[0], wf);
+  {
+    f32x4 na4[2][4];
+#pragma unroll
+    for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+      for (int g = 0; g < 4; ++g) na4[nb][g] = *reinterpret_cast<const f32x4*>(na + nb * 32 + 8 * g + 4 * h);
+    unsigned vmask = 0xffffffffu;  // this half's points below `valid`
+    if (valid < TP) {
+      vmask = 0;
+#pragma unroll
+      for (int i = 0; i < 32; ++i)
+        if ((i >> 4) * 32 + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h < valid) vmask |= 1u << i;
+    }
+    // candidates of the lane's channel as a 64-bit set: bit 32 h' + 16 nb + r, the same word in both half-waves
+#pragma unroll
+    for (int mb = 0; mb < MB; ++mb) {
+      float e1, e0;
+      screen_eps_coef<K>(nw[ch0 + mb * 32 + n], e1, e0);
+      float L = -INFINITY;
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) L = fmaxf(L, acc[mb][nb][r] - fmaf(e1, na4[nb][r >> 2][r & 3], e0));
+      L = fmaxf(L, swap32(L));
+      unsigned own = 0;
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r)
+          own |= (acc[mb][nb][r] + fmaf(e1, na4[nb][r >> 2][r & 3], e0) >= L) ? 1u << (nb * 16 + r) : 0u;
+      own &= vmask;
+      if (sc.probe_s) {  // tests only
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const size_t o = ((size_t)tile * 1024 + ch0 + mb * 32 + n) * TP + nb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+            sc.probe_s[o] = acc[mb][nb][r];
+            sc.probe_eps[o] = fmaf(e1, na4[nb][r >> 2][r & 3], e0);
+          }
+      }
+      const unsigned other = swap32(own);
+      unsigned long long m64 = h ? ((unsigned long long)own << 32) | other : ((unsigned long long)other << 32) | own;
+      if (m64 == 0) m64 = 1;  // NaN inputs only: keep the replay well defined
+      sets[mb * 64 + lane] = m64;
+    }
+  }
+#ifdef CATRE_DEBUG_TRACE
+  int tmax = 0;
+#endif
+#pragma unroll 1
+  for (int mb = 0; mb < MB; ++mb) {
+    const unsigned long long m64 = sets[mb * 64 + lane];
+    const float b = bias[ch0 + mb * 32 + n];
+    // trips of the m-block: wave maximum of ceil(candidates / 2) - lane half h replays the candidates of rank h, h + 2, ...
+    // so the two lanes of a channel share its work
+    int c = __popcll(m64);
+#ifdef CATRE_DEBUG_TRACE
+    if (h == 0) atomicAdd(&g_screen_cnt[c < 31 ? c : 31], 1ull);
+#endif
+    int trips = 1;  // (a ballot per step instead of a shuffle tree: no lane-address registers live across the sweep)
+    while (trips < TP / 2 && __ballot(c > 2 * trips)) ++trips;
+#ifdef CATRE_DEBUG_TRACE
+    if (lane == 0) atomicAdd(&g_screen_cnt[32 + (trips < 15 ? trips : 15)], 1ull);
+    tmax = trips > tmax ? trips : tmax;
+#endif
+    const int pad = __builtin_ctzll(m64);  // the channel's first candidate: an extra replay of a real point changes no maximum
+    unsigned long long m = m64;
+    if (h) m &= m - 1;  // rank 0 belongs to the lower half-wave
+    const f32x4* w = wf + (size_t)mb * (K / 8) * 64;
+    const f32x4* wn = mb + 1 < MB ? w + (K / 8) * 64 : w;
+    float best = -INFINITY;
+    // at most 64 / 2 / SCREEN_CMAX = 8 rounds (every point of the tile a candidate); one on all but degenerate tiles
+#pragma unroll 1
+    for (int done = 0; done < trips; done += SCREEN_CMAX) {
+      int p[SCREEN_CMAX];
+#pragma unroll
+      for (int j = 0; j < SCREEN_CMAX; ++j) {
+        const int bit = m ? __builtin_ctzll(m) : pad;
+        m &= m - 1;
+        m &= m - 1;
+        p[j] = ((bit >> 4) & 1) * 32 + (bit & 3) + 8 * ((bit & 15) >> 2) + 4 * (bit >> 5);
+      }
+      const int rem = trips - done;
+      const f32x4* nxt = rem > SCREEN_CMAX ? w : wn;
+      float v;
+      if (rem == 1)
+        v = screen_replay<1, NKC8>(w, nxt, wb, x, K, p);
+      else if (rem == 2)
+        v = screen_replay<2, NKC8>(w, nxt, wb, x, K, p);
+      else
+        v = screen_replay<SCREEN_CMAX, NKC8>(w, nxt, wb, x, K, p);
+      best = fmaxf(best, v);
+    }
+    best = fmaxf(best, swap32(best));
+    if (lane < 32) {
+      const float v = best + b;
+      out[ch0 + mb * 32 + lane] = relu ? fmaxf(v, 0.f) : v;
+    }
+  }
+#ifdef CATRE_DEBUG_TRACE
+  if (lane == 0) {
+    if (tmax > SCREEN_CMAX) atomicAdd(&g_screen_cnt[48], 1ull);
+    atomicAdd(&g_screen_cnt[49], 1ull);
+  }
+#endif
+}
+
+// ------------------------------------------------------------------------------------------
+// k_trunk4 with conv4 512 -> 1024 screened: conv1 .. conv3 and the a3 image are trunk4_body's; the last layer is the
+// split-bf16 screen over all 1024 x 64 outputs and the fp32 replay of the candidates.  Same bits as k_trunk4<false>.
+// ------------------------------------------------------------------------------------------
+struct Trunk4Screen {
+  ScreenArgs sc;
+  const f32x4* wf;  // fp32 fragments of the wave's channels (the replay reads them), + (lane & 31)
+  const float* b4;
+  ScreenPipe8<2> g4;
+  f32x16 acc4[8][2];
+  __device__ __forceinline__ void prefetch(const f32x4* __restrict__ wp4, const float* __restrict__ b4_, int mb0, int lane) {
+    wf = wp4 + ((size_t)mb0 * 64) * 64 + (lane & 31);
+    b4 = b4_;
+    g4.prefetch(sc.wps + ((size_t)mb0 * 32) * 64 + lane);
+  }
+  // a2 (32 KiB, dead): [0, 64) the row norms, from float 64 on the waves' candidate sets (4 x 4 KiB)
+  __device__ __forceinline__ void sweep(const float* a3, float* a2, int tid, int lane) {
+    screen_row_norms<512, 256>(a3, a2, tid);
+    __syncthreads();
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb) acc4[mb][0] = acc4[mb][1] = zero16();
+    g4.run(acc4, a3, lane);
+  }
+  __device__ __forceinline__ void store(const float* a3, float* a2, float* __restrict__ pm, int tile, int mb0, int valid, int,
+                                        const TrainSave&, int lane) {
+    unsigned long long* sets = reinterpret_cast<unsigned long long*>(a2 + 64) + (mb0 >> 3) * 8 * 64;
+    // The lane id is computed afresh here instead of being kept from the prologue (volatile: the compiler would otherwise merge
+    // the two) - the sweep above runs at exactly 256 VGPRs next to its 256 accumulators, and a lane id live across it is one
+    // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    screen_select_store<8, 512>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32, false, valid, tile, sc,
+                                lane);
+  }
+};
+
+__global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __restrict__ trans3,
+                                                 const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                 const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
+                                                 const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                                 const float* __restrict__ b3, const f32x4* __restrict__ wp4,
+                                                 const float* __restrict__ b4, float* __restrict__ pm,
+                                                 float* __restrict__ pointfeat, int B, int N, int M,
+                                                 unsigned long long* __restrict__ trace, ScreenArgs sc) {
+  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
+  Trunk4Screen tl;
+  tl.sc = sc;
+  trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
+                     TrainSave{}, tl);
+}

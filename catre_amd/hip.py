@@ -131,6 +131,7 @@ _SIGS = {
     "catre_linear_t": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "catre_stnkd_pool": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_trunk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
+    "catre_trunk_screen_probe": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_ts_head": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
     "catre_rot_head": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_rot_head_dim": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
@@ -242,6 +243,7 @@ _SIGS = {
     "catre_profile_collect": (_I, [_P, _I, _P]),
     "catre_debug_trunk_trace": (_I, [_P]),
     "catre_debug_knob": (_I, [_I, _I]),
+    "catre_debug_screen_counts": (_I, [_P, _I]),
     "catre_stream_capture_id": (_I, [_P, _P]),
     "catre_status_string": (ctypes.c_char_p, [_I]),
     "catre_version": (ctypes.c_char_p, []),
@@ -268,7 +270,7 @@ def bump_param_epoch():
     _param_epoch[0] += 1
 
 
-FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4}
+FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5}
 
 
 def form_switch(name, value=None):

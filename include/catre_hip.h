@@ -201,6 +201,16 @@ int catre_trunk(const catre_points* pts, const float* trans3, const float* trans
                 const float* const* params, const float* packed, float* gfeat, float* pointfeat,
                 void* workspace, size_t ws_bytes, int B, int N, int M, void* stream);
 
+/* Tests only - the error bound of the screened max-pool (kernel-form switch 5, csrc/catre_screen.h): one catre_trunk
+ * launch on the screened form of the trunk (full grids only, else CATRE_ERR_UNSUPPORTED; `packed` must hold
+ * CATRE_PACK_F32_ENCODER) that also writes, for conv4 and every (tile, channel, point), the split-bf16 screen value and
+ * the bound eps the device computed for it: screen, eps [tiles][1024][64] (tiles as in the workspace: B*ceil(N/64)
+ * observed tiles, then B*ceil(M/64) prior tiles; a ragged tile's points beyond its cloud repeat the last point).
+ * |conv4 output before bias - screen| <= eps must hold for every entry.  gfeat / pointfeat as catre_trunk. */
+int catre_trunk_screen_probe(const catre_points* pts, const float* trans3, const float* trans64,
+                             const float* const* params, const float* packed, float* screen, float* eps, float* gfeat,
+                             float* pointfeat, void* workspace, size_t ws_bytes, int B, int N, int M, void* stream);
+
 /* a7+a8: feature gather + FC_TransSizeHead.forward (CATRE_disR_shared.py:69-84,
  * heads/fc_trans_size_head.py:61-70).  -> trans_deltas [B,3], scale_deltas [B,3]. */
 int catre_ts_head(const float* gfeat, const float* init_pose, const float* init_scale,
@@ -285,9 +295,14 @@ typedef enum catre_kernel_id {
 int catre_profile_enable(int kernel_id, int max_records);
 /* Kernel-form switches (A/B measurements, tests): where a stage has more than one kernel form for full grids - all forms
  * give the same bits - `id` selects the switch (0: one-wave-per-SIMD trunk k_trunk4, 1: one-wave STN kernels, 2: STN kernels
- * on pairs of tiles, 3: one-wave rotation-head kernel k_rot_l1w, 4: one-launch FC tails of small batches k_fc_tail), `value` 1 / 0 sets it, value < 0 only queries.  Returns
- * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 on, 3 and 4 off - they
- * measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR = 0, CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
+ * on pairs of tiles, 3: one-wave rotation-head kernel k_rot_l1w, 4: one-launch FC tails of small batches k_fc_tail,
+ * 5: conv4's max-pool of the fp32 one-wave trunk screened with split-bf16 products and replayed in fp32 only where the
+ * error bound cannot rule a point out, k_trunk4s - same bits for FINITE activations; where the dense form returns Inf / NaN
+ * this one may return another value),
+ * `value` 1 / 0 sets it, value < 0 only queries.  Returns
+ * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5 on, 3 and 4 off -
+ * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN = 0,
+ * CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
  * launched with. */
 int catre_form_switch(int id, int value);
 /* Experiment knobs of the instrumented library (id 0: start offset in cycles between the co-resident workgroups of the
@@ -299,6 +314,10 @@ int catre_profile_collect(float* ms_out, int max_out, int* n_out);
 /* Debug aid: when non-NULL, every k_trunk workgroup writes 8 waves x 8 shader-clock stamps (u64) at its phase
  * boundaries into `device_buffer` ([tiles][8 waves][8]); NULL disables.  Process-global. */
 int catre_debug_trunk_trace(void* device_buffer);
+/* Instrumented library only (CATRE_ERR_UNSUPPORTED in the product): the screened form's counters since the last reset -
+ * out64[0..31] candidates per (tile, channel) (31: >= 31), [32..47] replay trips per (wave, tile, m-block) (47: >= 15),
+ * [48] (wave, tile) units in which an m-block needed more than one round of 4 trips, [49] all units. */
+int catre_debug_screen_counts(unsigned long long* out64, int reset);
 
 /* Identity of the stream capture `stream` is currently recording into (hipStreamGetCaptureInfo; 0 when the stream is not
  * capturing).  The host mirror keys its "this capture already recorded a weight-pack node" shortcut on it
