@@ -1618,8 +1618,8 @@ struct PackLayout {
   // fp16 fragment packs of the bf16 packs' matrices, same layout (CATRE_PACK_F16, CATRE_DTYPE_F16), offsets in floats
   size_t f16_stn_c2, f16_stn_c3, f16_fstn_c1, f16_fstn_c2, f16_fstn_c3, f16_c2, f16_c3, f16_c4, f16_rot_l0[2], f16_rot_l1[2];
   // screened max-pool of the fp32 path (catre_screen.h), part of the fp32 encoder pack: hi + lo bf16 fragments of conv4 and
-  // its weight-row norms
-  size_t scr_c4, scr_nw4;
+  // its weight-row norms; the same of stn.conv3 and fstn.conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
+  size_t scr_c4, scr_nw4, scr_stn_c3, scr_fstn_c3, scr_nw_stn, scr_nw_fstn;
 };
 
 PackLayout pack_layout(int ts_in) {
@@ -1680,6 +1680,10 @@ PackLayout pack_layout(int ts_in) {
   }
   L.scr_c4 = take(1024 * 512);
   L.scr_nw4 = take(1024);
+  L.scr_stn_c3 = take(1024 * 128);
+  L.scr_fstn_c3 = take(1024 * 128);
+  L.scr_nw_stn = take(1024);
+  L.scr_nw_fstn = take(1024);
   // everything above is independent of ts_in (the stage entry points rely on that)
   L.ts_w0t = take((size_t)ts_in * 256);
   L.ts_w1t = take(256 * 256);
@@ -1825,11 +1829,16 @@ static int bf_pair_min() {
 // exist for A/B measurements and for tests that compare the forms in one process).  Defaults: the encoder forms on,
 // k_rot_l1w OFF (it measured 8 % slower than k_rot_l1<1>: profiles/r06_rotw_phases.txt), k_fc_tail OFF (one object:
 // 0.643 vs 0.620 ms per K = 4 refine, profiles/r06_fc_tail_ab.jsonl), the screened conv4 max-pool k_trunk4s ON (30.7 vs 34.0 ms
-// per K = 4 refine at B = 256, profiles/screen_ab.jsonl); the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR /
-// CATRE_SCREEN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1) sets the process default once, catre_form_switch changes it at run time.
-enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32 };
+// per K = 4 refine at B = 256, profiles/screen_ab.jsonl), the screened conv3 max-pool of the STN pair kernels
+// (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl); the
+// environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN / CATRE_SCREEN_STN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
+// sets the process default once, catre_form_switch changes it at run time.
+enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64 };
 #ifndef CATRE_SCREEN_DEFAULT
 #define CATRE_SCREEN_DEFAULT true
+#endif
+#ifndef CATRE_SCREEN_STN_DEFAULT
+#define CATRE_SCREEN_STN_DEFAULT true
 #endif
 static std::atomic<int> g_forms{-1};
 static int forms() {
@@ -1841,7 +1850,8 @@ static int forms() {
     };
     v = (on("CATRE_TRUNK4") ? FORM_TRUNK4 : 0) | (on("CATRE_STN4") ? FORM_STN4 : 0) |
         (on("CATRE_STN_PAIR") ? FORM_STN_PAIR : 0) | (on("CATRE_ROTW", false) ? FORM_ROTW : 0) |
-        (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0);
+        (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0) |
+        (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0);
     g_forms.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -1852,6 +1862,8 @@ static bool stn_pair_on() { return forms() & FORM_STN_PAIR; }  // off: one tile 
 static bool stn4_on() { return forms() & FORM_STN4; }
 static bool fc_tail_on() { return forms() & FORM_FC_TAIL; }  // B <= 8: an FC tail as one launch (k_fc_tail); off (default: the fused form measured SLOWER, profiles/r06_fc_tail_ab.jsonl): three k_linear launches
 static bool screen_on() { return forms() & FORM_SCREEN; }  // fp32 full grids: conv4's max-pool screened on the bf16 pipe (k_trunk4s)
+// fp32 full-grid STN pair kernels: conv3's max-pool screened (k_stn*_pair_s); refines `screen`: CATRE_SCREEN = 0 turns both off
+static bool screen_stn_on() { return (forms() & (FORM_SCREEN | FORM_SCREEN_STN)) == (FORM_SCREEN | FORM_SCREEN_STN); }
 static bool rotw_on() { return forms() & FORM_ROTW; }  // rotation heads, one wave per SIMD (k_rot_l1w); off (default): k_rot_l1<1>
 
 // The measurement hooks are the library's only process-global mutable state.  They are fenced: compiled out entirely
@@ -1883,9 +1895,15 @@ struct ProfScope {
 #endif
 
 
+// full grids: the STN kernels on pairs of tiles
+static bool stn_pair_form(int tiles, int B, int N, int M) {
+  return row_split8(tiles) == 1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256;
+}
+
 // The three encoder kernels of one iteration (fp32 or split compute), tile partial maxima -> ws + W.pm
 void launch_stn3d(const catre_points* pts, const float* const* prm, const float* packed, float* ws, const WsLayout& W,
-                  int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr) {
+                  int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr, float* probe_s = nullptr,
+                  float* probe_eps = nullptr, float* probe_rows = nullptr) {
   const PackLayout L = pack_layout(1);  // conv offsets do not depend on ts_in
   const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
   ProfScope ps(CATRE_K_STN3D, st);
@@ -1896,7 +1914,12 @@ void launch_stn3d(const catre_points* pts, const float* const* prm, const float*
                      pkb(packed, L.sp_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
-  } else if (row_split8(tiles) == 1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256) {
+  } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
+    hipLaunchKernelGGL(k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
+                       prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
+                       prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M,
+                       ScreenArgs{pkb(packed, L.scr_stn_c3), packed + L.scr_nw_stn, probe_s, probe_eps}, probe_rows);
+  } else if (stn_pair_form(tiles, B, N, M)) {
     const int pairs = stn_pairs(B, N, M);  // (fewer pairs than CUs: one tile per workgroup keeps the whole chip busy)
     hipLaunchKernelGGL(k_stn3d_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B],
                        pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B],
@@ -1916,7 +1939,8 @@ void launch_stn3d(const catre_points* pts, const float* const* prm, const float*
 }
 
 void launch_stnkd(const catre_points* pts, const float* trans3, const float* const* prm, const float* packed, float* ws,
-                  const WsLayout& W, int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr) {
+                  const WsLayout& W, int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr,
+                  float* probe_s = nullptr, float* probe_eps = nullptr, float* probe_rows = nullptr) {
   const PackLayout L = pack_layout(1);
   const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
   ProfScope ps(CATRE_K_STNKD, st);
@@ -1928,7 +1952,12 @@ void launch_stnkd(const catre_points* pts, const float* trans3, const float* con
                      prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
-  } else if (row_split8(tiles) == 1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256) {
+  } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
+    hipLaunchKernelGGL(k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
+                       prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
+                       prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
+                       ScreenArgs{pkb(packed, L.scr_fstn_c3), packed + L.scr_nw_fstn, probe_s, probe_eps}, probe_rows);
+  } else if (stn_pair_form(tiles, B, N, M)) {
     const int pairs = stn_pairs(B, N, M);
     hipLaunchKernelGGL(k_stnkd_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B],
                        pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2), prm[CATRE_P_FSTN_CONV2_B],
@@ -2138,6 +2167,16 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
                        packed + L.scr_nw4);
   }
+  // the same of the two STNs' conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
+  frag_sp(prm[CATRE_P_STN_CONV3_W], 128, 1024, 128, L.scr_stn_c3);
+  frag_sp(prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128, L.scr_fstn_c3);
+  flush_lp(LP_SPLIT);
+  if (prm[CATRE_P_STN_CONV3_W])
+    hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_stn);
+  if (prm[CATRE_P_FSTN_CONV3_W])
+    hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_fstn);
   }
   for (int h = 0; h < 2 && head32; ++h) {
     const int base = h ? CATRE_P_ROTY_L0_W : CATRE_P_ROTX_L0_W;
@@ -2234,6 +2273,25 @@ int catre_trunk_screen_probe(const catre_points* pts, const float* trans3, const
   hipStream_t st = (hipStream_t)stream;
   launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st, screen, eps);
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
+  return check_launch();
+}
+
+int catre_stn_screen_probe(int which, const catre_points* pts, const float* trans3, const float* const* prm,
+                           const float* packed, float* screen, float* eps, float* rows, float* pooled, void* workspace,
+                           size_t ws_bytes, int B, int N, int M, void* stream) {
+  REQUIRE((which == 0 || which == 1) && pts && (which == 0 || trans3) && prm && packed && screen && eps && rows && pooled &&
+          workspace && dims_ok1(B, N, M));
+  const WsLayout W = ws_layout(B, N, M);
+  if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
+  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
+  if (!stn_pair_form(tiles, B, N, M)) return CATRE_ERR_UNSUPPORTED;  // the screened form exists for the full-grid pair kernels only
+  float* ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  if (which == 0)
+    launch_stn3d(pts, prm, packed, ws, W, B, N, M, false, st, nullptr, screen, eps, rows);
+  else
+    launch_stnkd(pts, trans3, prm, packed, ws, W, B, N, M, false, st, nullptr, screen, eps, rows);
+  hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, pooled, 1024, 1024, B, N, M);
   return check_launch();
 }
 
@@ -2752,7 +2810,7 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 5) return -1;
+  if (id < 0 || id > 6) return -1;
   const int bit = 1 << id;
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);
@@ -2782,17 +2840,17 @@ int catre_stream_capture_id(void* stream, unsigned long long* id_out) {
   return CATRE_OK;
 }
 
-int catre_debug_screen_counts(unsigned long long* out64, int reset) {
+int catre_debug_screen_counts(unsigned long long* out192, int reset) {
 #ifdef CATRE_DEBUG_TRACE
-  REQUIRE(out64);
-  if (hipMemcpyFromSymbol(out64, HIP_SYMBOL(g_screen_cnt), 64 * sizeof(unsigned long long)) != hipSuccess) return CATRE_ERR_LAUNCH;
+  REQUIRE(out192);
+  if (hipMemcpyFromSymbol(out192, HIP_SYMBOL(g_screen_cnt), 3 * 64 * sizeof(unsigned long long)) != hipSuccess) return CATRE_ERR_LAUNCH;
   if (reset) {
-    const unsigned long long z[64] = {};
+    const unsigned long long z[3 * 64] = {};
     if (hipMemcpyToSymbol(HIP_SYMBOL(g_screen_cnt), z, sizeof(z)) != hipSuccess) return CATRE_ERR_LAUNCH;
   }
   return CATRE_OK;
 #else
-  (void)out64;
+  (void)out192;
   (void)reset;
   return CATRE_ERR_UNSUPPORTED;
 #endif

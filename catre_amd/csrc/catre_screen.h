@@ -75,24 +75,28 @@ struct ScreenArgs {
 };
 
 #ifdef CATRE_DEBUG_TRACE
-// diagnostic build: [0..31] candidates per (tile, channel) (31: >= 31), [32..47] trips per (wave, tile, m-block)
-// (47: >= 15), [48] (wave, tile) units with an m-block of more than SCREEN_CMAX trips, [49] all units
-__device__ unsigned long long g_screen_cnt[64];
+// diagnostic build, one row per screened layer (0 trunk conv4, 1 stn conv3, 2 fstn conv3): [0..31] candidates per
+// (tile, channel) (31: >= 31), [32..47] trips per (wave, tile, m-block) (47: >= 15), [48] (wave, tile) units with an
+// m-block of more than SCREEN_CMAX trips, [49] all units
+__device__ unsigned long long g_screen_cnt[3][64];
 #endif
 
 #define SCREEN_CMAX 4  // replay chains a lane carries at once; an m-block that needs more trips takes further rounds
 
-// ||a(p)||_2 (rounded up) of the 64 rows of a swizzled [64][C] fp32 LDS image -> na[64]; NT threads, NT/64 per row
-template <int C, int NT>
-__device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, float* __restrict__ na, int tid) {
-  constexpr int PER = NT / 64, CH = C / 4 / PER;  // chunks of 4 floats per thread
+// Row addressing of the fp32 LDS image a screened layer reads: SWZ = the XOR-swizzled [rows][C] image of the trunk (pitch
+// C, chunk c of row r at c ^ (r & 15)), otherwise a padded image of pitch `ld` (the STN kernels' [128][LD128]).
+// ||a(p)||_2 (rounded up) of the ROWS rows of the image -> na[ROWS]; NT threads, NT/ROWS per row
+template <int C, int NT, int ROWS = 64, bool SWZ = true>
+__device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, float* __restrict__ na, int tid, int ld = C) {
+  constexpr int PER = NT / ROWS, CH = C / 4 / PER;  // chunks of 4 floats per thread
   static_assert(CH % 16 == 0, "a thread's chunks are whole swizzle groups");
   const int row = tid / PER, part = tid % PER;
-  const float* r = img + row * C + part * CH * 4;
+  const float* r = img + row * ld + part * CH * 4;
+  const int key = SWZ ? row & 15 : 0;
   float s = 0.f;
 #pragma unroll 8
   for (int j = 0; j < CH; ++j) {  // physical chunk j ^ (row & 15): the 16 rows of a lane group hit 16 distinct bank slots
-    const f32x4 v = *reinterpret_cast<const f32x4*>(r + ((j ^ (row & 15)) << 2));
+    const f32x4 v = *reinterpret_cast<const f32x4*>(r + ((j ^ key) << 2));
     s = fmaf(v[0], v[0], s);
     s = fmaf(v[1], v[1], s);
     s = fmaf(v[2], v[2], s);
@@ -103,12 +107,13 @@ __device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, 
   if (part == 0) na[row] = fmaf(sqrtf(s), 1.f + 0x1p-12f, 0x1p-58f);
 }
 
-// The screen sweep of an MB8 x NB2 wave tile over K = 512: split-bf16 A fragments from the pack, B fragments split in
-// registers from the fp32 swizzled LDS image [64][512] (there is no LDS left for hi / lo images beside it).
+// The screen sweep of an MB8 x NB2 wave tile over K = 16 NKC: split-bf16 A fragments from the pack, B fragments split in
+// registers from the fp32 LDS image - the trunk's swizzled [64][512] (there is no LDS left for hi / lo images beside it) or
+// a padded [64][LD] one (SWZ = false).
 // The weight ring works on HALF chunks (4 m-blocks x K=16: 24 MFMAs = 768 cycles), PFD of them in flight.
-template <int PFD>
+template <int PFD, int NKC_ = 32, bool SWZ = true, int LD = 512>
 struct ScreenPipe8 {
-  static constexpr int NKC = 32, NT = 2 * NKC, RA = PFD + 1, LO = 1024 * 512 / 8;
+  static constexpr int NKC = NKC_, NT = 2 * NKC, RA = PFD + 1, LO = 1024 * (16 * NKC) / 8;
   u32x4 ah[RA][4], al[RA][4];
   const u32x4* wp;
 
@@ -130,14 +135,15 @@ struct ScreenPipe8 {
   }
   __device__ __forceinline__ void run(f32x16 (&acc)[8][2], const float* x, int lane) {
     const int n = lane & 31, h = lane >> 5, sw = lane & 15;
-    const float* xrow = x + n * 512;
+    const float* xrow = x + n * LD;
     // k-slot order of the bf16 fragments: element e of lane half h is k = 16 kc + 8 (e >> 2) + 4 h + (e & 3), i.e. the fp32
     // chunks 4 kc + h and 4 kc + 2 + h of the row; the XOR touches the low four chunk bits only (see GemmPipe::run)
+    // (padded image: one row pointer, the chunk offsets are immediates)
     const float* xlow[4][2];
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-      for (int j = 0; j < 2; ++j) xlow[q][j] = xrow + (((4 * q + 2 * j + h) ^ sw) << 2);
+      for (int j = 0; j < 2; ++j) xlow[q][j] = SWZ ? xrow + (((4 * q + 2 * j + h) ^ sw) << 2) : xrow + ((2 * j + h) << 2);
     f32x4 braw[2][2];
     u32x4 bh[2][2], bl[2][2];  // [chunk parity][nb]
     auto issue_b = [&](int kc) {
@@ -145,7 +151,8 @@ struct ScreenPipe8 {
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
         for (int j = 0; j < 2; ++j)
-          braw[nb][j] = *reinterpret_cast<const f32x4*>(xlow[kc & 3][j] + (kc >> 2) * 64 + nb * 32 * 512);
+          braw[nb][j] = *reinterpret_cast<const f32x4*>((SWZ ? xlow[kc & 3][j] + (kc >> 2) * 64 : xlow[0][j] + kc * 16) +
+                                                        nb * 32 * LD);
     };
     auto split_b = [&](int kc) {
 #pragma unroll
@@ -204,9 +211,9 @@ __device__ __forceinline__ void screen_load_w(f32x4 (&wb)[16], const f32x4* __re
 // Replay of T outputs of ONE channel (this lane's) at points p[0..T): the fmaf chain of GemmPipe::run over K = 8 NKC8 * 8.
 //   w    : fp32 fragment image of the channel's m-block, + (lane & 31)   (float4 (kc * 64 + 32 h') = k 8kc + 4h' ..)
 //   wb   : wb[0] holds the first 8 chunks on entry (requested by the previous call); on exit it holds those of `wnext`
-//   x    : swizzled fp32 LDS image [64][ld]
+//   x    : fp32 LDS image [64][ld], swizzled or padded (SWZ)
 // returns the maximum of the T results
-template <int T, int NKC8>
+template <int T, int NKC8, bool SWZ = true>
 __device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, const f32x4* __restrict__ wnext,
                                                f32x4 (&wb)[2][16], const float* x, int ld, const int (&p)[SCREEN_CMAX]) {
   static_assert(NKC8 % 2 == 0 && (T == 1 || T == 2 || T == 4), "two blocks of 8 chunks per trip");
@@ -220,7 +227,7 @@ __device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, cons
   for (int j = 0; j < T; ++j) {
     y[j] = 0.f;
     row[j] = x + p[j] * ld;
-    key[j] = p[j] & 15;
+    key[j] = SWZ ? p[j] & 15 : 0;
   }
   f32x4 ab[2][SB][T][2];
   auto load_stage = [&](int buf, int b8, int st) {  // chunks kc = 8 b8 + SB st .. + SB
@@ -272,16 +279,17 @@ __device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, cons
 // Epilogue of a screened "swapped" MB x 2 wave tile: select, replay, store.  acc holds the screen values S of channels
 // ch0 + 32 mb + (lane & 31) at points 32 nb + (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
 //   wf  : fp32 fragment image of the layer, at the wave's first m-block, + (lane & 31);  K / 64 blocks of 8 chunks
-//   na  : LDS, [64] row norms (screen_row_norms); x: the fp32 image the screen read
+//   na  : LDS, [64] row norms (screen_row_norms); x: the fp32 image the screen read, pitch ld, swizzled or padded (SWZ)
 //   sets: LDS, this wave's [MB][64] candidate sets - the replay loop over the m-blocks is NOT unrolled (its body is the
 //         three replay forms: unrolled MB times it would not fit the instruction cache), so what the selection leaves per
 //         m-block goes through LDS instead of a register array
-template <int MB, int K>
+//   LAYER: the row of g_screen_cnt the instrumented build counts into
+template <int MB, int K, bool SWZ = true, int LAYER = 0>
 __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
                                                     const float* __restrict__ nw, const float* na, const float* x,
                                                     unsigned long long* sets, float* __restrict__ out,
                                                     const float* __restrict__ bias, int ch0, bool relu, int valid, int tile,
-                                                    const ScreenArgs& sc, int lane) {
+                                                    const ScreenArgs& sc, int lane, int ld = K) {
   constexpr int NKC8 = K / 64;
   const int n = lane & 31, h = lane >> 5;
   const int partner = (lane ^ 32) << 2;  // ds_bpermute address of the channel's other half-wave lane
@@ -347,12 +355,12 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
     // so the two lanes of a channel share its work
     int c = __popcll(m64);
 #ifdef CATRE_DEBUG_TRACE
-    if (h == 0) atomicAdd(&g_screen_cnt[c < 31 ? c : 31], 1ull);
+    if (h == 0) atomicAdd(&g_screen_cnt[LAYER][c < 31 ? c : 31], 1ull);
 #endif
     int trips = 1;  // (a ballot per step instead of a shuffle tree: no lane-address registers live across the sweep)
     while (trips < TP / 2 && __ballot(c > 2 * trips)) ++trips;
 #ifdef CATRE_DEBUG_TRACE
-    if (lane == 0) atomicAdd(&g_screen_cnt[32 + (trips < 15 ? trips : 15)], 1ull);
+    if (lane == 0) atomicAdd(&g_screen_cnt[LAYER][32 + (trips < 15 ? trips : 15)], 1ull);
     tmax = trips > tmax ? trips : tmax;
 #endif
     const int pad = __builtin_ctzll(m64);  // the channel's first candidate: an extra replay of a real point changes no maximum
@@ -376,11 +384,11 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
       const f32x4* nxt = rem > SCREEN_CMAX ? w : wn;
       float v;
       if (rem == 1)
-        v = screen_replay<1, NKC8>(w, nxt, wb, x, K, p);
+        v = screen_replay<1, NKC8, SWZ>(w, nxt, wb, x, ld, p);
       else if (rem == 2)
-        v = screen_replay<2, NKC8>(w, nxt, wb, x, K, p);
+        v = screen_replay<2, NKC8, SWZ>(w, nxt, wb, x, ld, p);
       else
-        v = screen_replay<SCREEN_CMAX, NKC8>(w, nxt, wb, x, K, p);
+        v = screen_replay<SCREEN_CMAX, NKC8, SWZ>(w, nxt, wb, x, ld, p);
       best = fmaxf(best, v);
     }
     best = fmaxf(best, swap32(best));
@@ -391,8 +399,8 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
   }
 #ifdef CATRE_DEBUG_TRACE
   if (lane == 0) {
-    if (tmax > SCREEN_CMAX) atomicAdd(&g_screen_cnt[48], 1ull);
-    atomicAdd(&g_screen_cnt[49], 1ull);
+    if (tmax > SCREEN_CMAX) atomicAdd(&g_screen_cnt[LAYER][48], 1ull);
+    atomicAdd(&g_screen_cnt[LAYER][49], 1ull);
   }
 #endif
 }
@@ -445,4 +453,139 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
   tl.sc = sc;
   trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
                      TrainSave{}, tl);
+}
+
+// ------------------------------------------------------------------------------------------
+// k_stn3d_pair / k_stnkd_pair (inference) with conv3 128 -> 1024 screened: conv1 / conv2 (and fstn.conv1) and the fp32
+// a2 / f2 image [128][LD128] are the dense kernels'; each tile of the pair is then screened on the MB8 x NB2 wave tile
+// (K = 128: 8 K = 16 chunks), selected and replayed like the trunk's conv4.  Same bits as k_stn*_pair<false>.
+// The B fragments are split in registers inside every wave, as in the trunk (ScreenPipe8): see DESIGN section 3.
+// ------------------------------------------------------------------------------------------
+typedef ScreenPipe8<2, 8, false, LD128> StnScreenPipe;
+
+// scratch: LDS that is dead after conv2 (a1 / h1, 34 KiB): [0, 128) the row norms of both tiles, from float 128 on the
+// waves' candidate sets (4 x 4 KiB).  g holds the first sweep's first weight fragments (requested in front of conv2).
+// probe_rows (tests only): the image rows as [tile][64][128]
+template <int LAYER>
+__device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnScreenPipe& g,
+                                                   const f32x4* __restrict__ wp3, const float* __restrict__ b3,
+                                                   float* __restrict__ pm, int tile0, int valid2, const ScreenArgs& sc,
+                                                   float* __restrict__ probe_rows, int wave, int tid, int lane) {
+  const int nt = valid2 > TP ? 2 : 1, mb0 = wave * 8;
+  screen_row_norms<128, 256, 2 * TP, false>(img, scratch, tid, LD128);
+  if (probe_rows) {
+    for (int i = tid; i < nt * TP * 32; i += 256)
+      *reinterpret_cast<f32x4*>(probe_rows + ((size_t)tile0 * TP + (i >> 5)) * 128 + (i & 31) * 4) =
+          *reinterpret_cast<const f32x4*>(img + (i >> 5) * LD128 + (i & 31) * 4);
+  }
+  __syncthreads();
+  unsigned long long* sets = reinterpret_cast<unsigned long long*>(scratch + 2 * TP) + wave * 8 * 64;
+  // The two tiles one after the other on the same accumulators, as two copies of the code: in a runtime loop the compiler
+  // hoists the selection's ~25 bit-mask constants and the lane-dependent addresses out of it, across the sweep, and spills.
+  auto tile = [&](int t, int ln) {
+    f32x16 acc[8][2];
+#pragma unroll
+    for (int mb = 0; mb < 8; ++mb) acc[mb][0] = acc[mb][1] = zero16();
+    const float* x = img + t * TP * LD128;
+    g.run(acc, x, ln);
+    // the lane id is computed afresh behind the sweep (see Trunk4Screen::store: the sweep leaves no register for it)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
+    const f32x4* wf = wp3 + ((size_t)mb0 * 16) * 64 + (ln & 31);
+    screen_select_store<8, 128, false, LAYER>(acc, wf, sc.nw, scratch + t * TP, x, sets, pm + (size_t)(tile0 + t) * PMW, b3,
+                                              mb0 * 32, true, min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128);
+  };
+  tile(0, lane);
+  if (nt == 2) {  // (again a fresh lane id: nothing lane-dependent of the first tile stays live across its epilogue)
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    g.prefetch(sc.wps + ((size_t)mb0 * 8) * 64 + lane);
+    tile(1, lane);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_stn3d_pair_s(catre_points P, const float* __restrict__ W1,
+                                                      const float* __restrict__ b1, const f32x4* __restrict__ wp2,
+                                                      const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                                      const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
+                                                      int M, ScreenArgs sc, float* __restrict__ probe_rows) {
+  __shared__ __attribute__((aligned(16))) float smem[2 * TP * LD64 + 2 * TP * LD128];
+  float* a1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
+  float* a2 = smem + 2 * TP * LD64;   // [128][132]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  TileInfo ti;
+  int tile0;
+  pair_info32(blockIdx.x, B, N, M, ti, tile0);
+
+  GemmPipe<1, 4, false, false, 8, 3> g2;  // conv2 64->128: wave -> m-block `wave`, all four point blocks
+  g2.prefetch(wp2 + (wave * 8) * 64 + lane, 0);
+  f32x4 bv2[1][4];
+  load_bias_quads<1>(bv2, b2, wave * 32, lane);
+  {  // conv1 3->64 on the VALU: thread = (point, 32-channel half)
+    const int p = (wave & 1) * TP + lane;
+    float x, y, z;
+    load_point(P, ti, p, x, y, z);
+    conv3_relu_row<32>(x, y, z, W1, b1, (wave >> 1) * 32, a1 + p * LD64);
+  }
+  __syncthreads();
+  StnScreenPipe g3;
+  g3.prefetch(sc.wps + ((size_t)wave * 8 * 8) * 64 + lane);
+  {
+    f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
+    g2.run(acc, a1, LD64, lane);
+    store_tile_lds_pre<1, 4, true, false>(acc, a2, LD128, wave * 32, bv2, lane);
+  }
+  __syncthreads();
+  stn_conv3_screened<1>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
+}
+
+__global__ __launch_bounds__(256) void k_stnkd_pair_s(catre_points P, const float* __restrict__ trans3,
+                                                      const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                      const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                      const f32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                      const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                      float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,
+                                                      float* __restrict__ probe_rows) {
+  __shared__ __attribute__((aligned(16))) float smem[4 * TP * LD64 + 2 * TP * LD128];
+  float* h1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
+  float* f1 = smem + 2 * TP * LD64;   // [128][68]
+  float* f2 = smem + 4 * TP * LD64;   // [128][132]
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  TileInfo ti;
+  int tile0;
+  pair_info32(blockIdx.x, B, N, M, ti, tile0);
+
+  const int mblk1 = wave >> 1, half1 = wave & 1;
+  GemmPipe<1, 2, false, false, 8, 4> g1;  // fstn.conv1 64->64: wave -> (m-block, tile of the pair)
+  g1.prefetch(wpf1 + (mblk1 * 8) * 64 + lane, 0);
+  f32x4 bv1[1][4];
+  load_bias_quads<1>(bv1, bf1, mblk1 * 32, lane);
+  {
+    const int p = (wave & 1) * TP + lane;
+    float x, y, z;
+    load_point(P, ti, p, x, y, z);
+    apply_t3(trans3 + ti.cloud * 9, x, y, z);
+    conv3_relu_row<32>(x, y, z, Wc1, bc1, (wave >> 1) * 32, h1 + p * LD64);
+  }
+  __syncthreads();
+  GemmPipe<1, 4, false, false, 8, 3> g2;
+  g2.prefetch(wpf2 + (wave * 8) * 64 + lane, 0);
+  f32x4 bv2[1][4];
+  load_bias_quads<1>(bv2, bf2, wave * 32, lane);
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    f32x16 acc[1][2] = {{zero16(), zero16()}};
+    g1.run(acc, h1 + half1 * TP * LD64, LD64, lane);
+    store_tile_lds_pre<1, 2, true, false>(acc, f1 + half1 * TP * LD64, LD64, mblk1 * 32, bv1, lane);
+  }
+  __syncthreads();
+  StnScreenPipe g3;
+  g3.prefetch(sc.wps + ((size_t)wave * 8 * 8) * 64 + lane);
+  {
+    f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
+    g2.run(acc, f1, LD64, lane);
+    store_tile_lds_pre<1, 4, true, false>(acc, f2, LD128, wave * 32, bv2, lane);
+  }
+  __syncthreads();
+  stn_conv3_screened<2>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
 }

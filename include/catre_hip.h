@@ -211,6 +211,16 @@ int catre_trunk_screen_probe(const catre_points* pts, const float* trans3, const
                              const float* const* params, const float* packed, float* screen, float* eps, float* gfeat,
                              float* pointfeat, void* workspace, size_t ws_bytes, int B, int N, int M, void* stream);
 
+/* Tests only - the same for conv3 of an STN on the screened full-grid pair kernels (kernel-form switch 6): `which` 0 =
+ * STN3d (trans3 unused), 1 = STNkd.  One catre_stn3d_pool / catre_stnkd_pool launch on k_stn3d_pair_s / k_stnkd_pair_s
+ * (CATRE_ERR_UNSUPPORTED where the full-grid pair form does not apply) that also writes screen, eps [tiles][1024][64] and
+ * rows [tiles][64][128]: the fp32 conv2 image rows the screen read (rows of points beyond a ragged tile repeat the last
+ * point; the rows of a second tile that does not exist are not written).  |conv3 output before bias - screen| <= eps
+ * must hold for every entry.  pooled as catre_stn3d_pool / catre_stnkd_pool. */
+int catre_stn_screen_probe(int which, const catre_points* pts, const float* trans3, const float* const* params,
+                           const float* packed, float* screen, float* eps, float* rows, float* pooled, void* workspace,
+                           size_t ws_bytes, int B, int N, int M, void* stream);
+
 /* a7+a8: feature gather + FC_TransSizeHead.forward (CATRE_disR_shared.py:69-84,
  * heads/fc_trans_size_head.py:61-70).  -> trans_deltas [B,3], scale_deltas [B,3]. */
 int catre_ts_head(const float* gfeat, const float* init_pose, const float* init_scale,
@@ -298,10 +308,13 @@ int catre_profile_enable(int kernel_id, int max_records);
  * on pairs of tiles, 3: one-wave rotation-head kernel k_rot_l1w, 4: one-launch FC tails of small batches k_fc_tail,
  * 5: conv4's max-pool of the fp32 one-wave trunk screened with split-bf16 products and replayed in fp32 only where the
  * error bound cannot rule a point out, k_trunk4s - same bits for FINITE activations; where the dense form returns Inf / NaN
- * this one may return another value),
+ * this one may return another value, 6: the same screen for conv3 of the two STNs on the full-grid pair kernels,
+ * k_stn3d_pair_s / k_stnkd_pair_s - it refines 5: the STN kernels are screened only while 5 and 6 are both on, so switch 5
+ * off turns every screened form off; the caveat about non-finite activations covers the STN layers too),
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
- * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5 on, 3 and 4 off -
- * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN = 0,
+ * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2, 5 and 6 on, 3 and 4 off -
+ * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
+ * CATRE_SCREEN_STN = 0,
  * CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
  * launched with. */
 int catre_form_switch(int id, int value);
@@ -314,10 +327,11 @@ int catre_profile_collect(float* ms_out, int max_out, int* n_out);
 /* Debug aid: when non-NULL, every k_trunk workgroup writes 8 waves x 8 shader-clock stamps (u64) at its phase
  * boundaries into `device_buffer` ([tiles][8 waves][8]); NULL disables.  Process-global. */
 int catre_debug_trunk_trace(void* device_buffer);
-/* Instrumented library only (CATRE_ERR_UNSUPPORTED in the product): the screened form's counters since the last reset -
- * out64[0..31] candidates per (tile, channel) (31: >= 31), [32..47] replay trips per (wave, tile, m-block) (47: >= 15),
+/* Instrumented library only (CATRE_ERR_UNSUPPORTED in the product): the screened forms' counters since the last reset,
+ * three rows of 64 (trunk conv4, stn.conv3, fstn.conv3) -
+ * row[0..31] candidates per (tile, channel) (31: >= 31), [32..47] replay trips per (wave, tile, m-block) (47: >= 15),
  * [48] (wave, tile) units in which an m-block needed more than one round of 4 trips, [49] all units. */
-int catre_debug_screen_counts(unsigned long long* out64, int reset);
+int catre_debug_screen_counts(unsigned long long* out192, int reset);
 
 /* Identity of the stream capture `stream` is currently recording into (hipStreamGetCaptureInfo; 0 when the stream is not
  * capturing).  The host mirror keys its "this capture already recorded a weight-pack node" shortcut on it

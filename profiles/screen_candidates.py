@@ -1,6 +1,7 @@
-"""Candidate-count histogram and further-rounds share of the screened trunk (kernel-form switch `screen`) on the bench inputs.
+"""Candidate-count histograms and further-rounds shares of the three screened layers (kernel-form switches `screen` and
+`screen_stn`: trunk conv4, stn.conv3, fstn.conv3) on the bench inputs.
 
-Needs the instrumented library (`make -C catre_amd/csrc TRACE=1`), whose k_trunk4s counts while it runs:
+Needs the instrumented library (`make -C catre_amd/csrc TRACE=1`), whose screened kernels count while they run:
     CATRE_HIP_LIB=catre_amd/csrc/libcatre_hip_trace.so python profiles/screen_candidates.py [out.txt]
 One K = 4 refine of the headline batch (B = 256, N = M = 1024, `synth.make_inputs(seed=1000)`, recipe weights)."""
 import ctypes
@@ -23,28 +24,32 @@ model.eval()
 batch = {k: v.cuda() for k, v in synth.make_inputs(B, N, M, seed=1000).items()}
 lib = hip.load()
 hip.form_switch("screen", True)
+hip.form_switch("screen_stn", True)
 model.refine(batch, n_iter=K)   # warm-up (packs the weights)
 torch.cuda.synchronize()
-cnt = (ctypes.c_ulonglong * 64)()
+cnt = (ctypes.c_ulonglong * (3 * 64))()
 hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts (needs the TRACE=1 library)")
 model.refine(batch, n_iter=K)
 torch.cuda.synchronize()
 hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts")
-c = list(cnt)
-lines = [f"screened trunk conv4, B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights"]
-tot = sum(c[:32])
-mean = sum(i * v for i, v in enumerate(c[:32])) / max(tot, 1)
-lines.append(f"candidates per (tile, channel): {tot} pairs, mean {mean:.4f} (bin 31 = 31 and more)")
-for i, v in enumerate(c[:32]):
-    if v:
-        lines.append(f"  {i:2d}: {v:10d}  {v / tot:.6f}")
-tt = sum(c[32:48])
-tmean = sum(i * v for i, v in enumerate(c[32:48])) / max(tt, 1)
-lines.append(f"replay trips per (wave, tile, 32-channel block): {tt} blocks, mean {tmean:.4f} (bin 15 = 15 and more)")
-for i, v in enumerate(c[32:48]):
-    if v:
-        lines.append(f"  {i:2d}: {v:10d}  {v / tt:.6f}")
-lines.append(f"(wave, tile) units with a block of more than 4 trips (a further replay round): {c[48]} of {c[49]} = {c[48] / max(c[49], 1):.5f}")
+lines = [f"B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights; replay chains a lane carries at once: 4"]
+for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_s)", "fstn.conv3 (k_stnkd_pair_s)")):
+    c = list(cnt)[64 * row:64 * row + 64]
+    lines.append(f"screened {name}")
+    tot = sum(c[:32])
+    mean = sum(i * v for i, v in enumerate(c[:32])) / max(tot, 1)
+    lines.append(f"candidates per (tile, channel): {tot} pairs, mean {mean:.4f} (bin 31 = 31 and more)")
+    for i, v in enumerate(c[:32]):
+        if v:
+            lines.append(f"  {i:2d}: {v:10d}  {v / tot:.6f}")
+    tt = sum(c[32:48])
+    tmean = sum(i * v for i, v in enumerate(c[32:48])) / max(tt, 1)
+    lines.append(f"replay trips per (wave, tile, 32-channel block): {tt} blocks, mean {tmean:.4f} (bin 15 = 15 and more)")
+    for i, v in enumerate(c[32:48]):
+        if v:
+            lines.append(f"  {i:2d}: {v:10d}  {v / tt:.6f}")
+    lines.append(f"(wave, tile) units with a block of more than 4 trips (a further replay round): {c[48]} of {c[49]} = "
+                 f"{c[48] / max(c[49], 1):.5f}")
 text = "\n".join(lines) + "\n"
 print(text, end="")
 if len(sys.argv) > 1:
