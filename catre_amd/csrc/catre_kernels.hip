@@ -2937,9 +2937,12 @@ struct PclWs {
   size_t bins, choose, offsets, total, cand, total_ints;
   int nchunks;
 };
+// frames the kernels index in int: H * W < 2^30, the product taken in size_t (65536 x 65536 wraps to 0 in int)
+inline bool pcl_frame_ok(int H, int W) { return H > 0 && W > 0 && (size_t)H * (size_t)W < ((size_t)1 << 30); }
 PclWs pcl_ws(int I, int H, int W) {
   PclWs L;
-  L.nchunks = (H * W + PCL_CHUNK - 1) / PCL_CHUNK;
+  const size_t HW = (size_t)H * (size_t)W;
+  L.nchunks = (int)((HW + PCL_CHUNK - 1) / PCL_CHUNK);
   size_t o = 0;
   auto take = [&](size_t n) {
     size_t r = o;
@@ -2950,7 +2953,7 @@ PclWs pcl_ws(int I, int H, int W) {
   L.choose = take(I);
   L.offsets = take((size_t)I * L.nchunks);
   L.total = take(I);
-  L.cand = take((size_t)I * H * W);
+  L.cand = take((size_t)I * HW);
   L.total_ints = o;
   return L;
 }
@@ -2958,14 +2961,14 @@ inline PclCam pcl_cam(const float* K9) { return PclCam{K9[0], K9[4], K9[2], K9[5
 }  // namespace
 
 size_t catre_pcl_workspace_bytes(int I, int H, int W) {
-  if (I <= 0 || H <= 0 || W <= 0) return 0;
+  if (I <= 0 || !pcl_frame_ok(H, W)) return 0;  // the limit catre_pcl_candidates enforces: no size for a frame it refuses
   return pcl_ws(I, H, W).total_ints * sizeof(int);
 }
 
 int catre_pcl_candidates(const float* depth, const float* K9, const unsigned char* masks, const float* poses,
                          const float* scales, float ratio, int use_ball, int I, int H, int W, void* workspace,
                          size_t ws_bytes, int32_t* counts_out, void* stream) {
-  REQUIRE(depth && K9 && poses && scales && workspace && I > 0 && H > 0 && W > 0 && (size_t)H * W < (1u << 30));
+  REQUIRE(depth && K9 && poses && scales && workspace && I > 0 && pcl_frame_ok(H, W));
   const PclWs L = pcl_ws(I, H, W);
   if (ws_bytes < L.total_ints * sizeof(int)) return CATRE_ERR_WORKSPACE;
   int* ws = (int*)workspace;
@@ -2986,7 +2989,7 @@ int catre_pcl_candidates(const float* depth, const float* K9, const unsigned cha
 int catre_pcl_sample(const float* depth, const float* K9, const void* workspace, size_t ws_bytes,
                      const long long* sample_idx, unsigned long long seed, int I, int H, int W, int N, float* pcl_out,
                      int32_t* pix_out, void* stream) {
-  REQUIRE(depth && K9 && workspace && pcl_out && I > 0 && H > 0 && W > 0 && N > 0);
+  REQUIRE(depth && K9 && workspace && pcl_out && I > 0 && pcl_frame_ok(H, W) && N > 0);
   const PclWs L = pcl_ws(I, H, W);
   if (ws_bytes < L.total_ints * sizeof(int)) return CATRE_ERR_WORKSPACE;
   const int* ws = (const int*)workspace;
@@ -2999,7 +3002,7 @@ int catre_pcl_sample(const float* depth, const float* K9, const void* workspace,
 // catre_pcl_sample).  scratch: I * 4 * slot_cap floats, slot_cap >= the largest tiled list (count doubled until >= N).
 int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, size_t ws_bytes, int I, int H, int W, int N,
                   float* scratch, int slot_cap, long long* sample_idx_out, void* stream) {
-  REQUIRE(depth && K9 && workspace && scratch && sample_idx_out && I > 0 && H > 0 && W > 0 && N > 0 && slot_cap > 0);
+  REQUIRE(depth && K9 && workspace && scratch && sample_idx_out && I > 0 && pcl_frame_ok(H, W) && N > 0 && slot_cap > 0);
   const PclWs L = pcl_ws(I, H, W);
   if (ws_bytes < L.total_ints * sizeof(int)) return CATRE_ERR_WORKSPACE;
   const int* ws = (const int*)workspace;

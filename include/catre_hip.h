@@ -767,7 +767,9 @@ int catre_init_noise(const float* pose, const float* euler_deg, const float* tra
  * use_ball = 0 keeps every valid pixel (crop_mask_depth_image, :352-377).  depth [H,W] fp32 metres (device),
  * K9 = HOST 3x3 intrinsics row-major, masks [I,H,W] bytes (device) or NULL, poses [I,3,4], scales [I,3] (device).
  * The ordered (row-major, = torch.nonzero order) candidate lists stay in `workspace`
- * (catre_pcl_workspace_bytes); counts_out [I] (device, optional) receives their lengths. */
+ * (catre_pcl_workspace_bytes); counts_out [I] (device, optional) receives their lengths.
+ * Pixels are indexed in int: H * W < 2^30 (the product taken in size_t).  catre_pcl_workspace_bytes returns 0 for
+ * I, H or W <= 0 and for a frame at or over that limit; the three entry points below refuse such a frame. */
 size_t catre_pcl_workspace_bytes(int I, int H, int W);
 int catre_pcl_candidates(const float* depth, const float* K9, const unsigned char* masks, const float* poses,
                          const float* scales, float ratio, int use_ball, int I, int H, int W, void* workspace,
