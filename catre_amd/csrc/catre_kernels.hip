@@ -3025,7 +3025,7 @@ static int loss_fwd_impl(const float* pose, const float* scale, const float* gt_
                          const float* gt_scale, const float* kps, const float* cands, const unsigned char* valid,
                          const int32_t* is_sym, const catre_loss_cfg2& cfg, int32_t* best, int32_t* counts, float* part_ws,
                          float* losses, const float* trans_deltas, const int32_t* terms, int n_terms, float* prefix, int B,
-                         int M, int S1, void* stream, int nl, int np) {
+                         int M, int S1, void* stream, int nl, int np, const int32_t* n_obj = nullptr) {
   REQUIRE(pose && scale && gt_rot && gt_trans && gt_scale && is_sym && best && counts && part_ws && losses && B > 0 && S1 > 0);
   REQUIRE(cfg.pm_mode >= 0 && cfg.pm_mode < CATRE_PM_MODE_COUNT && cfg.pm_elem >= 0 && cfg.pm_elem < CATRE_PM_ELEM_COUNT);
   if (cfg.base.pm_on) {
@@ -3042,14 +3042,14 @@ static int loss_fwd_impl(const float* pose, const float* scale, const float* gt_
   hipLaunchKernelGGL(k_loss_fwd, dim3(B), dim3(256), 0, st, pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, valid,
                      is_sym, cfg, best, part_ws, B, M, S1, np);
   hipLaunchKernelGGL(k_loss_reduce, dim3(1), dim3(512), 0, st, (const float*)part_ws, is_sym, cfg, losses, counts, B, M,
-                     pose, gt_trans, trans_deltas, order, n_terms, prefix, np, nl);
+                     pose, gt_trans, trans_deltas, order, n_terms, prefix, np, nl, n_obj);
   return check_launch();
 }
 static int loss_bwd_impl(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
                          const float* gt_scale, const float* kps, const float* cands, const int32_t* is_sym,
                          const int32_t* best, const int32_t* counts, const float* upstream, const float* const* up_prefix,
                          const int32_t* terms, int n_terms, const catre_loss_cfg2& cfg, float* dpose, float* dscale, int B,
-                         int M, int S1, void* stream, int nl) {
+                         int M, int S1, void* stream, int nl, const int32_t* n_obj = nullptr) {
   REQUIRE(pose && scale && gt_rot && gt_trans && gt_scale && is_sym && best && counts && (upstream || up_prefix) && dpose &&
           dscale && B > 0 && S1 > 0);
   REQUIRE(cfg.pm_mode >= 0 && cfg.pm_mode < CATRE_PM_MODE_COUNT && cfg.pm_elem >= 0 && cfg.pm_elem < CATRE_PM_ELEM_COUNT);
@@ -3067,7 +3067,7 @@ static int loss_bwd_impl(const float* pose, const float* scale, const float* gt_
   }
   hipLaunchKernelGGL(k_loss_bwd, dim3(B), dim3(256), 0, (hipStream_t)stream, pose, scale, gt_rot, gt_trans, gt_scale, kps,
                      cands, is_sym, best, upstream, cfg, counts, dpose, dscale, B, M, S1, upp, order, up_prefix ? n_terms : 0,
-                     nl);
+                     nl, n_obj);
   return check_launch();
 }
 extern "C" {
@@ -3132,6 +3132,27 @@ int catre_loss_bwd2(const float* pose, const float* scale, const float* gt_rot, 
   REQUIRE(cfg);
   return loss_bwd_impl(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts, upstream, up_prefix, terms,
                        n_terms, *cfg, dpose, dscale, B, M, S1, stream, LOSS_NL2);
+}
+
+// ... with the object count on the device: B is the capacity the launches are sized for, *n_obj (1 .. B) the objects that count
+int catre_loss_fwd3(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const unsigned char* valid,
+                    const int32_t* is_sym, const catre_loss_cfg2* cfg, int32_t* best, int32_t* counts, float* part_ws,
+                    float* losses, const float* trans_deltas, const int32_t* terms, int n_terms, float* prefix, int B,
+                    int M, int S1, const int32_t* n_obj, void* stream) {
+  REQUIRE(cfg && n_obj);
+  return loss_fwd_impl(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, valid, is_sym, *cfg, best, counts, part_ws, losses,
+                       trans_deltas, terms, n_terms, prefix, B, M, S1, stream, LOSS_NL2, LOSS_NP2, n_obj);
+}
+
+int catre_loss_bwd3(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const int32_t* is_sym,
+                    const int32_t* best, const int32_t* counts, const float* upstream, const float* const* up_prefix,
+                    const int32_t* terms, int n_terms, const catre_loss_cfg2* cfg, float* dpose, float* dscale, int B,
+                    int M, int S1, const int32_t* n_obj, void* stream) {
+  REQUIRE(cfg && n_obj);
+  return loss_bwd_impl(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts, upstream, up_prefix, terms,
+                       n_terms, *cfg, dpose, dscale, B, M, S1, stream, LOSS_NL2, n_obj);
 }
 
 int catre_init_noise(const float* pose, const float* euler_deg, const float* trans_noise, float max_rot_deg,

@@ -317,16 +317,19 @@ __global__ __launch_bounds__(256) void k_loss_fwd(const float* __restrict__ pose
 // is_sym.  (A single wave walking the objects in order was 2 x 16 dependent L2 round trips: 13.5 us.)
 // nl = LOSS_NL: losses[6 + 14] as the first entry points lay it out; LOSS_NL2: losses[8 + 14], slots 6, 7 = PM terms 1, 2.
 __global__ __launch_bounds__(512) void k_loss_reduce(const float* __restrict__ part, const int* __restrict__ is_sym, LossCfg cfg,
-                                                     float* __restrict__ losses, int* __restrict__ counts, int B, int M,
+                                                     float* __restrict__ losses, int* __restrict__ counts, int B_cap, int M,
                                                      const float* __restrict__ pose, const float* __restrict__ gt_trans,
                                                      const float* __restrict__ trans_deltas, unsigned term_order = 0,
                                                      int n_terms = 0, float* __restrict__ prefix = nullptr, int np = LOSS_NP,
-                                                     int nl = LOSS_NL) {
+                                                     int nl = LOSS_NL, const int* __restrict__ n_obj = nullptr) {
   static_assert(LOSS_NP == 8 && LOSS_NP2 <= 16, "eight waves: one per column of the first eight, one more pass for the rest");
   static_assert(LOSS_NL2 * 4 <= 32, "term_order packs four bits per term");
   __shared__ float colsum[LOSS_NP2];
   __shared__ float lossv[LOSS_NL2];
   __shared__ int nsym_s;
+  // the *3 entry points: objects 0 .. *n_obj - 1 of the B rows count (one plain load, the same value in every lane); the
+  // walk below is then the walk of a plain call on those rows, addition for addition
+  const int B = n_obj ? min(*n_obj, B_cap) : B_cap;  // (a count above the capacity must not walk off the buffers)
   {
     const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
     float s = 0.f, c = 0.f;
@@ -416,10 +419,19 @@ __global__ __launch_bounds__(256) void k_loss_bwd(const float* __restrict__ pose
                                                   const float* __restrict__ cands, const int* __restrict__ is_sym,
                                                   const int* __restrict__ best, const float* __restrict__ up_, LossCfg cfg,
                                                   const int* __restrict__ counts, float* __restrict__ dpose /*[B,3,4]*/,
-                                                  float* __restrict__ dscale, int B, int M, int S1,
+                                                  float* __restrict__ dscale, int B_cap, int M, int S1,
                                                   const LossUpPrefix up_prefix = LossUpPrefix{}, unsigned term_order = 0,
-                                                  int n_terms = 0, int nl = LOSS_NL) {
+                                                  int n_terms = 0, int nl = LOSS_NL,
+                                                  const int* __restrict__ n_obj = nullptr) {
   __shared__ float red[4];
+  // the *3 entry points: *n_obj objects count (uniform over the workgroup); a row past them gets exact +0 - it is written,
+  // not skipped, because the caller's dpose / dscale are uninitialised
+  const int B = n_obj ? min(*n_obj, B_cap) : B_cap;  // (a count above the capacity must not walk off the buffers)
+  if ((int)blockIdx.x >= B) {
+    if (threadIdx.x < 12) dpose[blockIdx.x * 12 + threadIdx.x] = 0.f;
+    if (threadIdx.x < 3) dscale[blockIdx.x * 3 + threadIdx.x] = 0.f;
+    return;
+  }
   // effective upstream of loss i: its own (up_in, optional) plus that of every prefix sum it is part of (k >= its position)
   float up[LOSS_NL2];
   {

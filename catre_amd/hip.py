@@ -236,6 +236,8 @@ _SIGS = {
     "catre_loss_bwd_sums": (_I, [_P] * 13 + [_I, _P, _P, _P, _I, _I, _I, _P]),
     "catre_loss_fwd2": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),
     "catre_loss_bwd2": (_I, [_P] * 13 + [_I, _P, _P, _P, _I, _I, _I, _P]),
+    "catre_loss_fwd3": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P, _P]),
+    "catre_loss_bwd3": (_I, [_P] * 13 + [_I, _P, _P, _P, _I, _I, _I, _P, _P]),
     # evaluation (include/catre_hip.h "evaluation of refined poses", catre_amd/evaluation.py)
     "catre_eval_overlaps": (_I, [_P] * 14 + [_I] * 6 + [_P]),
     "catre_eval_match_iou": (_I, [_P] * 7 + [_I] * 6 + [_P]),

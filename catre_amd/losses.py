@@ -8,6 +8,8 @@ device->host copy per refine iteration) and then evaluates the terms with ~100 s
 whole loss is two HIP launches forward (``catre_loss_fwd2``: candidate arg-max, the point-matching sums and the
 per-object terms in one workgroup per object, then an ordered reduction) and one backward (``catre_loss_bwd2``),
 chained into autograd by :class:`_FusedLoss`; no value ever leaves the device.  Every form takes the same launches.
+A batch padded to a fixed capacity (a captured graph whose object count changes per replay) passes the count in a device
+int (``SymTensors.n_obj`` -> ``catre_loss_fwd3`` / ``catre_loss_bwd3``): rows past it add nothing and get no gradient.
 """
 import ctypes
 
@@ -117,7 +119,8 @@ class _FusedLoss(torch.autograd.Function):
     ((0 + l[t0]) + l[t1]) + ... of the terms the loss dict will hold, in its order (see :class:`_LossTerm`)."""
 
     @staticmethod
-    def forward(ctx, pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, valid, is_sym, lcfg, trans_deltas, terms):
+    def forward(ctx, pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, valid, is_sym, lcfg, trans_deltas, terms,
+                n_obj=None):
         lib = hip.load()
         # PM_USE_BBOX: the eight cube corners are generated in the kernel, obj_kps is not read (pm_loss.py:114-117)
         B, M, S1 = pose.shape[0], (8 if lcfg.pm_use_bbox else kps.shape[1] if kps is not None else 0), cands.shape[1]
@@ -130,13 +133,16 @@ class _FusedLoss(torch.autograd.Function):
         n = len(terms)
         buf = torch.empty(N_LOSS + N_VIS + n, dtype=torch.float32, device=dev)
         tarr = (ctypes.c_int32 * max(n, 1))(*terms)
-        hip.check(lib.catre_loss_fwd2(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
-                                      hip.ptr(kps), hip.ptr(cands), hip.ptr(valid), hip.ptr(is_sym), ctypes.byref(lcfg),
-                                      hip.ptr(best), hip.ptr(counts), hip.ptr(part), hip.ptr(buf), hip.ptr(trans_deltas),
-                                      tarr, n, hip.ptr(buf[N_LOSS + N_VIS:]) if n else None, B, M, S1, hip.stream_ptr(dev)),
-                  "catre_loss_fwd2")
-        ctx.save_for_backward(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts)
-        ctx.lcfg, ctx.dims, ctx.terms = lcfg, (B, M, S1), tuple(terms)
+        head = (hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale), hip.ptr(kps),
+                hip.ptr(cands), hip.ptr(valid), hip.ptr(is_sym), ctypes.byref(lcfg), hip.ptr(best), hip.ptr(counts),
+                hip.ptr(part), hip.ptr(buf), hip.ptr(trans_deltas), tarr, n, hip.ptr(buf[N_LOSS + N_VIS:]) if n else None,
+                B, M, S1)
+        if n_obj is None:
+            hip.check(lib.catre_loss_fwd2(*head, hip.stream_ptr(dev)), "catre_loss_fwd2")
+        else:  # B is the capacity, the count is read on the device
+            hip.check(lib.catre_loss_fwd3(*head, hip.ptr(n_obj), hip.stream_ptr(dev)), "catre_loss_fwd3")
+        ctx.save_for_backward(pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts, n_obj)
+        ctx.lcfg, ctx.dims, ctx.terms, ctx.n_in = lcfg, (B, M, S1), tuple(terms), 12 if n_obj is None else 13
         ctx.set_materialize_grads(False)
         losses, vis = buf[:N_LOSS], buf[N_LOSS:N_LOSS + N_VIS]
         ctx.mark_non_differentiable(vis)
@@ -147,8 +153,8 @@ class _FusedLoss(torch.autograd.Function):
     @staticmethod
     def backward(ctx, up, _up_vis, *up_sums):
         if up is None and all(u is None for u in up_sums):
-            return (None,) * 12
-        pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts = ctx.saved_tensors
+            return (None,) * ctx.n_in
+        pose, scale, gt_rot, gt_trans, gt_scale, kps, cands, is_sym, best, counts, n_obj = ctx.saved_tensors
         B, M, S1 = ctx.dims
         lib = hip.load()
         up = up.contiguous() if up is not None else None
@@ -157,12 +163,15 @@ class _FusedLoss(torch.autograd.Function):
         ups = [u.reshape(1).float().contiguous() if u is not None else None for u in up_sums]   # (no-ops for fp32 scalars)
         parr = (ctypes.c_void_p * max(n, 1))(*[u.data_ptr() if u is not None else None for u in ups])
         dpose, dscale = torch.empty_like(pose), torch.empty_like(scale)
-        hip.check(lib.catre_loss_bwd2(hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale),
-                                      hip.ptr(kps), hip.ptr(cands), hip.ptr(is_sym), hip.ptr(best), hip.ptr(counts),
-                                      hip.ptr(up), parr if any(u is not None for u in ups) else None, tarr, n,
-                                      ctypes.byref(ctx.lcfg), hip.ptr(dpose), hip.ptr(dscale), B, M, S1,
-                                      hip.stream_ptr(pose.device)), "catre_loss_bwd2")
-        return (dpose, dscale) + (None,) * 10
+        head = (hip.ptr(pose), hip.ptr(scale), hip.ptr(gt_rot), hip.ptr(gt_trans), hip.ptr(gt_scale), hip.ptr(kps),
+                hip.ptr(cands), hip.ptr(is_sym), hip.ptr(best), hip.ptr(counts), hip.ptr(up),
+                parr if any(u is not None for u in ups) else None, tarr, n, ctypes.byref(ctx.lcfg), hip.ptr(dpose),
+                hip.ptr(dscale), B, M, S1)
+        if n_obj is None:
+            hip.check(lib.catre_loss_bwd2(*head, hip.stream_ptr(pose.device)), "catre_loss_bwd2")
+        else:  # rows past the count are written as zeros
+            hip.check(lib.catre_loss_bwd3(*head, hip.ptr(n_obj), hip.stream_ptr(pose.device)), "catre_loss_bwd3")
+        return (dpose, dscale) + (None,) * (ctx.n_in - 2)
 
 
 _ADDS = (torch.Tensor.add, torch.Tensor.__add__, torch.Tensor.__radd__, torch.add)
@@ -226,25 +235,65 @@ class SymTensors:
     """Symmetry info already on the device (what :func:`catre_loss` builds from the python list): ``cands``
     [B,S1,3,3] with the identity first, ``valid`` [B,S1] uint8, ``is_sym`` [B] int32.  Passing this instead of the list
     keeps the call free of host->device copies (HIP-graph capture); both rotation terms are then always reported
-    (a term without objects is 0)."""
+    (a term without objects is 0).
 
-    def __init__(self, cands, valid, is_sym):
-        self.cands, self.valid, self.is_sym = cands, valid, is_sym
+    ``n_obj`` (optional): a 1-element int32 device tensor, ``1 <= n_obj <= B``.  The batch is then B rows of CAPACITY of
+    which the first ``n_obj`` are objects: only they enter the losses, the counts and the mean ``vis/`` scalars (which carry
+    the bits of a call on those rows alone) and only they receive gradient - the rows behind get exact zeros.  The value
+    is read on the device when the kernels run, so a captured graph follows it from replay to replay."""
+
+    def __init__(self, cands, valid, is_sym, n_obj=None):
+        if n_obj is not None and (not isinstance(n_obj, torch.Tensor) or n_obj.dtype != torch.int32 or n_obj.numel() != 1):
+            raise TypeError("n_obj: a 1-element int32 tensor on the device of the batch")
+        self.cands, self.valid, self.is_sym, self.n_obj = cands, valid, is_sym, n_obj
 
     @classmethod
-    def from_list(cls, sym_infos, device, s1=None):
+    def from_list(cls, sym_infos, device, s1=None, n_obj=None):
+        """``n_obj``: None, the tensor described above, or a python int that is put into a new one."""
+        if n_obj is not None and not isinstance(n_obj, torch.Tensor):
+            if not 1 <= int(n_obj) <= len(sym_infos):
+                raise ValueError(f"n_obj = {n_obj} outside 1 .. {len(sym_infos)} (the rows of sym_infos)")
+            n_obj = torch.tensor([int(n_obj)], dtype=torch.int32, device=device)
         cands, valid, is_sym = _sym_tensor(list(sym_infos), device, torch.float32)
         if s1 is not None and cands.shape[1] < s1:  # pad to a fixed candidate count
             pad = s1 - cands.shape[1]
             eye = torch.eye(3, device=device).expand(cands.shape[0], pad, 3, 3)
             cands = torch.cat([cands, eye], 1).contiguous()
             valid = torch.cat([valid, torch.zeros(valid.shape[0], pad, dtype=valid.dtype, device=device)], 1).contiguous()
-        return cls(cands, valid, is_sym)
+        return cls(cands, valid, is_sym, n_obj)
 
 
 N_VIS = 14
 VIS_KEYS = ("error_R", "error_t", "error_tx", "error_ty", "error_tz", "tx_pred", "ty_pred", "tz_pred", "tx_delta", "ty_delta",
             "tz_delta", "tx_gt", "ty_gt", "tz_gt")
+
+
+def loss_block(vis):
+    """The N_LOSS loss slots and the N_VIS scalars of one call as ONE contiguous [N_LOSS + N_VIS] tensor (they are
+    neighbours in the buffer the loss kernels write): what a training loop logs per iteration, copied with one launch.
+    ``vis``: the scalar tensor :func:`catre_loss` returned (``model.vis_scalars.tensor``)."""
+    vis = vis.detach()
+    assert vis.numel() == N_VIS and vis.storage_offset() >= N_LOSS
+    return torch.as_strided(vis, (N_LOSS + N_VIS,), (1,), vis.storage_offset() - N_LOSS)
+
+
+def loss_block_keys(cfg):
+    """Names of the N_LOSS + N_VIS columns of :func:`loss_block` under ``cfg``: the loss dict's key for each slot the
+    configuration fills (None for one it leaves 0), then ``vis/<name>``."""
+    lcfg = _loss_cfg_struct(cfg)
+    names = [None] * N_LOSS
+    if lcfg.pm_on:
+        for k, i in PM_KEYS[lcfg.pm_mode]:
+            names[i] = k
+    if lcfg.rot_on:
+        names[1], names[2] = "loss_rot", "loss_yaxis_rot"
+    if lcfg.trans_on:
+        names[3] = "loss_trans_xy" if lcfg.trans_split else "loss_trans_LPnP"
+        if lcfg.trans_split:
+            names[4] = "loss_trans_z"
+    if lcfg.scale_on:
+        names[5] = "loss_scale"
+    return tuple(names) + tuple(f"vis/{k}" for k in VIS_KEYS)
 
 
 class VisScalars:
@@ -271,14 +320,19 @@ def catre_loss(cfg, out_rot, out_trans, out_scale, gt_rot, gt_trans, gt_scale, o
     """-> the reference's loss dict (same keys, same values).  Gradients flow to out_rot / out_trans / out_scale.
     ``return_vis``: also return the 14 logging scalars (device tensor, see :class:`VisScalars`).
     ``pose``: the [B,3,4] tensor out_rot / out_trans are the slices of (the model's own call): the kernels take it as it is
-    instead of a cat of the two slices, and its gradient arrives whole instead of through two zero-fill + copy + add chains."""
+    instead of a cat of the two slices, and its gradient arrives whole instead of through two zero-fill + copy + add chains.
+    ``sym_info``: the reference's list, or a :class:`SymTensors`; one with ``n_obj`` set makes the B rows a capacity of which
+    the first ``n_obj`` count (what the rows behind hold changes no loss bit and they get zero gradient)."""
     lc = cfg.MODEL.CATRE.LOSS_CFG
     B = out_rot.shape[0]
     dev = out_rot.device
     if lc.PM_LW > 0:
         assert (obj_kps is not None) and (gt_trans is not None) and (gt_rot is not None)
+    n_obj = None
     if isinstance(sym_info, SymTensors):
-        cands, valid, is_sym = sym_info.cands, sym_info.valid, sym_info.is_sym
+        cands, valid, is_sym, n_obj = sym_info.cands, sym_info.valid, sym_info.is_sym, sym_info.n_obj
+        if n_obj is not None and n_obj.device != dev:
+            raise ValueError(f"n_obj lives on {n_obj.device}, the batch on {dev}")
         n_sym = n_nonsym = 1  # unknown on the host: report both rotation terms
     else:
         sym_info = list(sym_info) if sym_info is not None else [None] * B
@@ -308,7 +362,8 @@ def catre_loss(cfg, out_rot, out_trans, out_scale, gt_rot, gt_trans, gt_scale, o
     if lcfg.scale_on:
         keys.append(("loss_scale", 5))
     losses, vis, *prefix = _FusedLoss.apply(hip.require_dev_f32(pose, "pose"), f32(out_scale), f32(gt_rot), f32(gt_trans), gs,
-                                           f32(obj_kps), cands, valid, is_sym, lcfg, td, [i for _, i in keys])
+                                           f32(obj_kps), cands, valid, is_sym, lcfg, td, [i for _, i in keys],
+                                           *(() if n_obj is None else (n_obj,)))
     losses = losses.unbind(0)  # 0-dim views; their backward is one stack instead of six zero-fill + index + add chains
     tok = object()
     sums = [t.as_subclass(_LossTerm) for t in prefix]

@@ -904,6 +904,23 @@ int catre_loss_bwd2(const float* pose, const float* scale, const float* gt_rot, 
                     const int32_t* terms, int n_terms, const catre_loss_cfg2* cfg, float* dpose, float* dscale, int B,
                     int M, int S1, void* stream);
 
+/* ---- the same loss for a batch padded to a fixed capacity (a captured HIP graph whose object count changes per replay) --
+ * The arguments of the *2 pair plus n_obj: ONE int32 on the device, 1 <= *n_obj <= B, read when the kernels run.  B stays
+ * the capacity that sizes the launches, part_ws, best, dpose and dscale.  Only objects b < *n_obj enter the sums and the
+ * counts (counts[1] = *n_obj - counts[0]) and *n_obj stands wherever the *2 pair divides by B: losses, scalars and prefix
+ * sums carry the bits of a *2 call on the first *n_obj rows, and so do dpose / dscale of those rows.  Rows b >= *n_obj
+ * of dpose / dscale are written as +0; what the inputs hold there does not matter as long as it can be read. */
+int catre_loss_fwd3(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const unsigned char* valid,
+                    const int32_t* is_sym, const catre_loss_cfg2* cfg, int32_t* best, int32_t* counts, float* part_ws,
+                    float* losses, const float* trans_deltas, const int32_t* terms, int n_terms, float* prefix, int B,
+                    int M, int S1, const int32_t* n_obj, void* stream);
+int catre_loss_bwd3(const float* pose, const float* scale, const float* gt_rot, const float* gt_trans,
+                    const float* gt_scale, const float* kps, const float* cands, const int32_t* is_sym,
+                    const int32_t* best, const int32_t* counts, const float* upstream, const float* const* up_prefix,
+                    const int32_t* terms, int n_terms, const catre_loss_cfg2* cfg, float* dpose, float* dscale, int B,
+                    int M, int S1, const int32_t* n_obj, void* stream);
+
 /* ---- evaluation of refined poses: 3D IoU, degree / cm, greedy matching (core/catre/engine/test_utils.py:523-757) ------
  * What compute_independent_mAP (test_utils.py:760-924) does per image and class, for every image, class, evaluated refine
  * iteration and threshold in three launches.  The per-class AP integration (:112-137) and every ordering by score stay on
