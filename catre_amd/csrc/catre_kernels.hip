@@ -1830,15 +1830,21 @@ static int bf_pair_min() {
 // k_rot_l1w OFF (it measured 8 % slower than k_rot_l1<1>: profiles/r06_rotw_phases.txt), k_fc_tail OFF (one object:
 // 0.643 vs 0.620 ms per K = 4 refine, profiles/r06_fc_tail_ab.jsonl), the screened conv4 max-pool k_trunk4s ON (30.7 vs 34.0 ms
 // per K = 4 refine at B = 256, profiles/screen_ab.jsonl), the screened conv3 max-pool of the STN pair kernels
-// (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl); the
-// environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN / CATRE_SCREEN_STN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
+// (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl), the
+// pooled replay of the screened kernels (k_trunk4sp / k_stn*_pair_sp, only together with the screens they refine) ON (24.55 vs
+// 28.70 ms, profiles/screen_pool_ab.jsonl); the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
+// CATRE_SCREEN_STN / CATRE_SCREEN_POOL = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
 // sets the process default once, catre_form_switch changes it at run time.
-enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64 };
+enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64,
+       FORM_SCREEN_POOL = 128 };
 #ifndef CATRE_SCREEN_DEFAULT
 #define CATRE_SCREEN_DEFAULT true
 #endif
 #ifndef CATRE_SCREEN_STN_DEFAULT
 #define CATRE_SCREEN_STN_DEFAULT true
+#endif
+#ifndef CATRE_SCREEN_POOL_DEFAULT
+#define CATRE_SCREEN_POOL_DEFAULT true
 #endif
 static std::atomic<int> g_forms{-1};
 static int forms() {
@@ -1851,7 +1857,8 @@ static int forms() {
     v = (on("CATRE_TRUNK4") ? FORM_TRUNK4 : 0) | (on("CATRE_STN4") ? FORM_STN4 : 0) |
         (on("CATRE_STN_PAIR") ? FORM_STN_PAIR : 0) | (on("CATRE_ROTW", false) ? FORM_ROTW : 0) |
         (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0) |
-        (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0);
+        (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0) |
+        (on("CATRE_SCREEN_POOL", CATRE_SCREEN_POOL_DEFAULT) ? FORM_SCREEN_POOL : 0);
     g_forms.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -1864,6 +1871,17 @@ static bool fc_tail_on() { return forms() & FORM_FC_TAIL; }  // B <= 8: an FC ta
 static bool screen_on() { return forms() & FORM_SCREEN; }  // fp32 full grids: conv4's max-pool screened on the bf16 pipe (k_trunk4s)
 // fp32 full-grid STN pair kernels: conv3's max-pool screened (k_stn*_pair_s); refines `screen`: CATRE_SCREEN = 0 turns both off
 static bool screen_stn_on() { return (forms() & (FORM_SCREEN | FORM_SCREEN_STN)) == (FORM_SCREEN | FORM_SCREEN_STN); }
+// the screened kernels replay their candidates from one list per wave (k_trunk4sp); refines `screen`
+static bool screen_pool_on() { return forms() & FORM_SCREEN_POOL; }
+// ... and the STN pair kernels (k_stn*_pair_sp): with `screen_stn` as well.  Its own default so that the two kernel families
+// can follow their own A/B (CATRE_SCREEN_POOL_STN_DEFAULT)
+#ifndef CATRE_SCREEN_POOL_STN_DEFAULT
+#define CATRE_SCREEN_POOL_STN_DEFAULT true
+#endif
+static bool screen_pool_stn_on() {
+  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_POOL_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_POOL_STN_DEFAULT; }();
+  return screen_pool_on() && stn;
+}
 static bool rotw_on() { return forms() & FORM_ROTW; }  // rotation heads, one wave per SIMD (k_rot_l1w); off (default): k_rot_l1<1>
 
 // The measurement hooks are the library's only process-global mutable state.  They are fenced: compiled out entirely
@@ -1915,7 +1933,7 @@ void launch_stn3d(const catre_points* pts, const float* const* prm, const float*
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    hipLaunchKernelGGL(k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
+    hipLaunchKernelGGL(screen_pool_stn_on() ? k_stn3d_pair_sp : k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
                        prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
                        prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M,
                        ScreenArgs{pkb(packed, L.scr_stn_c3), packed + L.scr_nw_stn, probe_s, probe_eps}, probe_rows);
@@ -1953,7 +1971,7 @@ void launch_stnkd(const catre_points* pts, const float* trans3, const float* con
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    hipLaunchKernelGGL(k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
+    hipLaunchKernelGGL(screen_pool_stn_on() ? k_stnkd_pair_sp : k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
                        prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
                        prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
                        ScreenArgs{pkb(packed, L.scr_fstn_c3), packed + L.scr_nw_fstn, probe_s, probe_eps}, probe_rows);
@@ -1993,8 +2011,8 @@ void launch_trunk(const catre_points* pts, const float* trans3, const float* tra
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
   } else if (row_split8(tiles) == 1 && trunk4_on() && (screen_on() || probe_s)) {
-    hipLaunchKernelGGL(k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
+    hipLaunchKernelGGL(screen_pool_on() ? k_trunk4sp : k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64,
+                       prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
                        prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
                        g_trunk_trace, ScreenArgs{pkb(packed, L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps});
   } else if (row_split8(tiles) == 1 && trunk4_on()) {
@@ -2810,7 +2828,7 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 6) return -1;
+  if (id < 0 || id > 7) return -1;
   const int bit = 1 << id;
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);
@@ -2821,6 +2839,7 @@ int catre_debug_knob(int id, int value) {
 #ifdef CATRE_DEBUG_TRACE
   if (id == 0) return hipMemcpyToSymbol(HIP_SYMBOL(g_dephase_cycles), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
   if (id == 1) return hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
+  if (id == 2) return hipMemcpyToSymbol(HIP_SYMBOL(g_screen_count_on), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
   return CATRE_ERR_BAD_ARG;
 #else
   (void)id;

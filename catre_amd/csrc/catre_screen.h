@@ -77,8 +77,16 @@ struct ScreenArgs {
 #ifdef CATRE_DEBUG_TRACE
 // diagnostic build, one row per screened layer (0 trunk conv4, 1 stn conv3, 2 fstn conv3): [0..31] candidates per
 // (tile, channel) (31: >= 31), [32..47] trips per (wave, tile, m-block) (47: >= 15), [48] (wave, tile) units with an
-// m-block of more than SCREEN_CMAX trips, [49] all units
+// m-block of more than SCREEN_CMAX trips, [49] all units.  Pooled form: [32..47] rounds of 64 entries per (wave, tile),
+// [48] units that needed more than one batch, [50] sum of entries, [51] sum of rounds
 __device__ unsigned long long g_screen_cnt[3][64];
+// counting on / off (catre_debug_knob 2): the counters' atomics cost far more than the epilogue they count in, so the
+// phase stamps of profiles/trace_trunk.py are taken with them off
+__device__ int g_screen_count_on = 1;
+#define SCREEN_COUNT(layer, bin, v)                                        \
+  do {                                                                     \
+    if (g_screen_count_on) atomicAdd(&g_screen_cnt[layer][bin], (unsigned long long)(v)); \
+  } while (0)
 #endif
 
 #define SCREEN_CMAX 4  // replay chains a lane carries at once; an m-block that needs more trips takes further rounds
@@ -276,6 +284,188 @@ __device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, cons
   return m;
 }
 
+// ------------------------------------------------------------------------------------------
+// Pooled replay (kernel-form switch `screen_pool`): the wave's 256 channels share ONE list of (channel, point) candidates,
+// replayed in rounds of 64 T entries - every lane carries T chains of ANY channels, so no lane idles because its own
+// channel has fewer candidates than the worst one of its m-block.  Each chain is the same fmaf chain as screen_replay's.
+//
+// LDS of a wave (its 4 KiB of candidate sets): [0, 2 KiB) one 64-bit set per channel, [2 KiB, 4 KiB) the list of
+// SCREEN_POOL_CAP 32-bit entries (channel << 8 | point); a chain's result is written back over its entry.
+// ------------------------------------------------------------------------------------------
+#define SCREEN_POOL_CAP 512
+static_assert(SCREEN_POOL_CAP >= 64 && SCREEN_POOL_CAP * 4 + 256 * 8 <= 8 * 64 * 8, "a channel's 64 candidates fit; list + sets fit the wave's 4 KiB");
+
+// One round: entries [e0 + 64 j + lane], j < T, of list[0 .. total).  A lane without an entry replays entry e0 and drops the
+// result.  wbase: fp32 fragment image of the wave's first m-block (no lane offset).
+// Weights: ring of RING blocks of WB chunks per chain, requested WL blocks ahead of their use (L2); LDS rows AL blocks ahead.
+template <int T, int K, bool SWZ>
+__device__ __forceinline__ void screen_replay_pool(const f32x4* __restrict__ wbase, const float* x, int ld, unsigned* list,
+                                                   int e0, int total, int lane) {
+  // (K = 128, the STN kernels: their epilogue keeps more values live across the replay - a shorter lead, or it spills)
+  constexpr int WB = 2, RING = 4, WL = K >= 512 ? 3 : 2, AL = K >= 512 ? 2 : 1, NKC8 = K / 64;
+  static_assert(WB * RING == 8, "one trip of the loop is one group of 8 chunks (64 floats of a row)");
+  float y[T];
+  const f32x4* w[T];
+  const float* row[T];
+  int key[T];
+  bool live[T];
+#pragma unroll
+  for (int j = 0; j < T; ++j) {
+    const int idx = e0 + 64 * j + lane;
+    live[j] = idx < total;
+    const unsigned ent = list[live[j] ? idx : e0];
+    const int cw = ent >> 8, p = ent & 63;
+    y[j] = 0.f;
+    w[j] = wbase + (size_t)(cw >> 5) * (K / 8) * 64 + (cw & 31);
+    row[j] = x + p * ld;
+    key[j] = SWZ ? p & 15 : 0;
+  }
+  f32x4 wv[RING][WB][T][2], ab[RING][WB][T][2];
+  auto load_w = [&](int slot, int g8, int b) {  // chunks kc = 8 g8 + WB b .. + WB
+#pragma unroll
+    for (int i = 0; i < WB; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e) wv[slot][i][j][e] = w[j][(g8 * 8 + WB * b + i) * 64 + 32 * e];
+  };
+  auto load_a = [&](int slot, int g8, int b) {
+#pragma unroll
+    for (int i = 0; i < WB; ++i)
+#pragma unroll
+      for (int j = 0; j < T; ++j)
+#pragma unroll
+        for (int e = 0; e < 2; ++e)
+          ab[slot][i][j][e] = *reinterpret_cast<const f32x4*>(row[j] + g8 * 64 + (((2 * (WB * b + i) + e) ^ key[j]) << 2));
+  };
+#pragma unroll
+  for (int b = 0; b < WL; ++b) load_w(b, 0, b);
+#pragma unroll
+  for (int b = 0; b < AL; ++b) load_a(b, 0, b);
+  __builtin_amdgcn_sched_barrier(0);
+#pragma unroll 1
+  for (int g8 = 0; g8 < NKC8; ++g8) {
+    const int gn = g8 + 1 < NKC8 ? g8 + 1 : 0;  // (behind the last group: reads of group 0 that nothing uses)
+#pragma unroll
+    for (int b = 0; b < RING; ++b) {
+      load_w((b + WL) % RING, b + WL < RING ? g8 : gn, (b + WL) % RING);
+      load_a((b + AL) % RING, b + AL < RING ? g8 : gn, (b + AL) % RING);
+      __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+      for (int i = 0; i < WB; ++i)
+#pragma unroll
+        for (int j = 0; j < T; ++j)
+#pragma unroll
+          for (int s = 0; s < 4; ++s) {
+            y[j] = fmaf(wv[b][i][j][0][s], ab[b][i][j][0][s], y[j]);
+            y[j] = fmaf(wv[b][i][j][1][s], ab[b][i][j][1][s], y[j]);
+          }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  }
+#pragma unroll
+  for (int j = 0; j < T; ++j)
+    if (live[j]) list[e0 + 64 * j + lane] = __float_as_uint(y[j]);
+}
+
+// Replay + store of the wave's 256 channels from their candidate sets sets[0 .. 256) (channel 32 mb + n of the wave at
+// index 32 mb + n).  Lane l owns channels 4 l .. 4 l + 3: counts, list offsets (exclusive prefix in channel order), the scan
+// of the results and the store.  A batch is the longest run of whole channels from `start` whose entries fit the list:
+// one batch on all but tie-heavy tiles, at most 32 (every channel has <= 64 entries, so a batch holds >= 8 channels).
+template <int K, bool SWZ, int LAYER>
+__device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbase, const float* x, int ld,
+                                                  unsigned long long* sets, float* __restrict__ out,
+                                                  const float* __restrict__ bias, int ch0, bool relu, int lane) {
+  unsigned* list = reinterpret_cast<unsigned*>(sets + 256);
+  float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+#ifdef CATRE_DEBUG_TRACE
+  int entries = 0, rounds = 0, batches = 0;
+#endif
+  int start = 0;
+#pragma unroll 1
+  while (start < 256) {
+    int c[4], off[4], s = 0;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      c[j] = 4 * lane + j >= start ? __popcll(sets[4 * lane + j]) : 0;
+      s += c[j];
+    }
+    int incl = s;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+      const int t = __shfl_up(incl, o);
+      if (lane >= o) incl += t;
+    }
+    // channels whose inclusive prefix fits: a prefix [0, end) of the channels (those below `start` count 0 entries)
+    int run = incl - s, end = 0, last[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      off[j] = run;
+      run += c[j];
+      last[j] = run;
+      end += __popcll(__ballot(run <= SCREEN_POOL_CAP));
+    }
+    const int sel = (end - 1) & 3;
+    const int total = __shfl(sel == 0 ? last[0] : sel == 1 ? last[1] : sel == 2 ? last[2] : last[3], (end - 1) >> 2);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int cw = 4 * lane + j;
+      if (cw >= start && cw < end) {
+        unsigned long long m = sets[cw];
+        int o = off[j];
+        while (m) {
+          const int bit = __builtin_ctzll(m);
+          m &= m - 1;
+          const int p = ((bit >> 4) & 1) * 32 + (bit & 3) + 8 * ((bit & 15) >> 2) + 4 * (bit >> 5);
+          list[o++] = (unsigned)(cw << 8 | p);
+        }
+      }
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll 1
+    for (int e0 = 0; e0 < total; e0 += 128) {
+      if (total - e0 > 64)
+        screen_replay_pool<2, K, SWZ>(wbase, x, ld, list, e0, total, lane);
+      else
+        screen_replay_pool<1, K, SWZ>(wbase, x, ld, list, e0, total, lane);
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+      const int cw = 4 * lane + j;
+      if (cw >= start && cw < end)
+        for (int i = 0; i < c[j]; ++i) best[j] = fmaxf(best[j], __uint_as_float(list[off[j] + i]));
+    }
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+#ifdef CATRE_DEBUG_TRACE
+    entries += total;
+    rounds += (total + 63) >> 6;
+    ++batches;
+#endif
+    start = end;
+  }
+  const f32x4 b = *reinterpret_cast<const f32x4*>(bias + ch0 + 4 * lane);
+  f32x4 v;
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    v[j] = best[j] + b[j];
+    if (relu) v[j] = fmaxf(v[j], 0.f);
+  }
+  *reinterpret_cast<f32x4*>(out + ch0 + 4 * lane) = v;
+#ifdef CATRE_DEBUG_TRACE
+  if (lane == 0) {
+    SCREEN_COUNT(LAYER, 32 + (rounds < 15 ? rounds : 15), 1ull);
+    if (batches > 1) SCREEN_COUNT(LAYER, 48, 1ull);
+    SCREEN_COUNT(LAYER, 49, 1ull);
+    SCREEN_COUNT(LAYER, 50, entries);
+    SCREEN_COUNT(LAYER, 51, rounds);
+  }
+#endif
+}
+
 // Epilogue of a screened "swapped" MB x 2 wave tile: select, replay, store.  acc holds the screen values S of channels
 // ch0 + 32 mb + (lane & 31) at points 32 nb + (r & 3) + 8 (r >> 2) + 4 (lane >> 5).
 //   wf  : fp32 fragment image of the layer, at the wave's first m-block, + (lane & 31);  K / 64 blocks of 8 chunks
@@ -284,7 +474,9 @@ __device__ __forceinline__ float screen_replay(const f32x4* __restrict__ w, cons
 //         three replay forms: unrolled MB times it would not fit the instruction cache), so what the selection leaves per
 //         m-block goes through LDS instead of a register array
 //   LAYER: the row of g_screen_cnt the instrumented build counts into
-template <int MB, int K, bool SWZ = true, int LAYER = 0>
+//   POOL : the candidates of the wave's MB * 32 = 256 channels are replayed from one list (screen_pool_store); the selection is
+//          the same, `sets` then holds one set per channel at [mb * 32 + n]
+template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false>
 __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
                                                     const float* __restrict__ nw, const float* na, const float* x,
                                                     unsigned long long* sets, float* __restrict__ out,
@@ -296,7 +488,7 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
   auto swap32 = [&](auto v) { return __builtin_bit_cast(decltype(v), __builtin_amdgcn_ds_bpermute(partner, __builtin_bit_cast(int, v))); };
   // first weight chunks of the replay: requested before the selection arithmetic
   f32x4 wb[2][16];
-  screen_load_w(wb[0], wf);
+  if constexpr (!POOL) screen_load_w(wb[0], wf);
   {
     f32x4 na4[2][4];
 #pragma unroll
@@ -341,8 +533,23 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
       const unsigned other = swap32(own);
       unsigned long long m64 = h ? ((unsigned long long)own << 32) | other : ((unsigned long long)other << 32) | own;
       if (m64 == 0) m64 = 1;  // NaN inputs only: keep the replay well defined
-      sets[mb * 64 + lane] = m64;
+      if constexpr (POOL) {
+#ifdef CATRE_DEBUG_TRACE
+        const int c = __popcll(m64);
+        if (h == 0) SCREEN_COUNT(LAYER, c < 31 ? c : 31, 1ull);
+#endif
+        sets[mb * 32 + n] = m64;  // (both half-waves: the same word)
+      } else {
+        sets[mb * 64 + lane] = m64;
+      }
     }
+  }
+  if constexpr (POOL) {
+    static_assert(MB == 8, "lane l owns channels 4 l .. 4 l + 3 of the wave's 256");
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    screen_pool_store<K, SWZ, LAYER>(wf - n, x, ld, sets, out, bias, ch0, relu, lane);
+    return;
   }
 #ifdef CATRE_DEBUG_TRACE
   int tmax = 0;
@@ -355,12 +562,12 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
     // so the two lanes of a channel share its work
     int c = __popcll(m64);
 #ifdef CATRE_DEBUG_TRACE
-    if (h == 0) atomicAdd(&g_screen_cnt[LAYER][c < 31 ? c : 31], 1ull);
+    if (h == 0) SCREEN_COUNT(LAYER, c < 31 ? c : 31, 1ull);
 #endif
     int trips = 1;  // (a ballot per step instead of a shuffle tree: no lane-address registers live across the sweep)
     while (trips < TP / 2 && __ballot(c > 2 * trips)) ++trips;
 #ifdef CATRE_DEBUG_TRACE
-    if (lane == 0) atomicAdd(&g_screen_cnt[LAYER][32 + (trips < 15 ? trips : 15)], 1ull);
+    if (lane == 0) SCREEN_COUNT(LAYER, 32 + (trips < 15 ? trips : 15), 1ull);
     tmax = trips > tmax ? trips : tmax;
 #endif
     const int pad = __builtin_ctzll(m64);  // the channel's first candidate: an extra replay of a real point changes no maximum
@@ -399,8 +606,8 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
   }
 #ifdef CATRE_DEBUG_TRACE
   if (lane == 0) {
-    if (tmax > SCREEN_CMAX) atomicAdd(&g_screen_cnt[LAYER][48], 1ull);
-    atomicAdd(&g_screen_cnt[LAYER][49], 1ull);
+    if (tmax > SCREEN_CMAX) SCREEN_COUNT(LAYER, 48, 1ull);
+    SCREEN_COUNT(LAYER, 49, 1ull);
   }
 #endif
 }
@@ -409,7 +616,8 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
 // k_trunk4 with conv4 512 -> 1024 screened: conv1 .. conv3 and the a3 image are trunk4_body's; the last layer is the
 // split-bf16 screen over all 1024 x 64 outputs and the fp32 replay of the candidates.  Same bits as k_trunk4<false>.
 // ------------------------------------------------------------------------------------------
-struct Trunk4Screen {
+template <bool POOL>
+struct Trunk4ScreenT {
   ScreenArgs sc;
   const f32x4* wf;  // fp32 fragments of the wave's channels (the replay reads them), + (lane & 31)
   const float* b4;
@@ -435,10 +643,11 @@ struct Trunk4Screen {
     // the two) - the sweep above runs at exactly 256 VGPRs next to its 256 accumulators, and a lane id live across it is one
     // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-    screen_select_store<8, 512>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32, false, valid, tile, sc,
-                                lane);
+    screen_select_store<8, 512, true, 0, POOL>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32, false,
+                                               valid, tile, sc, lane);
   }
 };
+typedef Trunk4ScreenT<false> Trunk4Screen;
 
 __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __restrict__ trans3,
                                                  const float* __restrict__ trans64, const float* __restrict__ Wc1,
@@ -455,6 +664,22 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
                      TrainSave{}, tl);
 }
 
+// the same kernel with the pooled replay (screen_pool_store)
+__global__ __launch_bounds__(256) void k_trunk4sp(catre_points P, const float* __restrict__ trans3,
+                                                  const float* __restrict__ trans64, const float* __restrict__ Wc1,
+                                                  const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
+                                                  const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                                  const float* __restrict__ b3, const f32x4* __restrict__ wp4,
+                                                  const float* __restrict__ b4, float* __restrict__ pm,
+                                                  float* __restrict__ pointfeat, int B, int N, int M,
+                                                  unsigned long long* __restrict__ trace, ScreenArgs sc) {
+  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
+  Trunk4ScreenT<true> tl;
+  tl.sc = sc;
+  trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
+                     TrainSave{}, tl);
+}
+
 // ------------------------------------------------------------------------------------------
 // k_stn3d_pair / k_stnkd_pair (inference) with conv3 128 -> 1024 screened: conv1 / conv2 (and fstn.conv1) and the fp32
 // a2 / f2 image [128][LD128] are the dense kernels'; each tile of the pair is then screened on the MB8 x NB2 wave tile
@@ -466,7 +691,7 @@ typedef ScreenPipe8<2, 8, false, LD128> StnScreenPipe;
 // scratch: LDS that is dead after conv2 (a1 / h1, 34 KiB): [0, 128) the row norms of both tiles, from float 128 on the
 // waves' candidate sets (4 x 4 KiB).  g holds the first sweep's first weight fragments (requested in front of conv2).
 // probe_rows (tests only): the image rows as [tile][64][128]
-template <int LAYER>
+template <int LAYER, bool POOL>
 __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnScreenPipe& g,
                                                    const f32x4* __restrict__ wp3, const float* __restrict__ b3,
                                                    float* __restrict__ pm, int tile0, int valid2, const ScreenArgs& sc,
@@ -491,7 +716,7 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
     // the lane id is computed afresh behind the sweep (see Trunk4Screen::store: the sweep leaves no register for it)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     const f32x4* wf = wp3 + ((size_t)mb0 * 16) * 64 + (ln & 31);
-    screen_select_store<8, 128, false, LAYER>(acc, wf, sc.nw, scratch + t * TP, x, sets, pm + (size_t)(tile0 + t) * PMW, b3,
+    screen_select_store<8, 128, false, LAYER, POOL>(acc, wf, sc.nw, scratch + t * TP, x, sets, pm + (size_t)(tile0 + t) * PMW, b3,
                                               mb0 * 32, true, min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128);
   };
   tile(0, lane);
@@ -502,11 +727,13 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
   }
 }
 
-__global__ __launch_bounds__(256) void k_stn3d_pair_s(catre_points P, const float* __restrict__ W1,
-                                                      const float* __restrict__ b1, const f32x4* __restrict__ wp2,
-                                                      const float* __restrict__ b2, const f32x4* __restrict__ wp3,
-                                                      const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
-                                                      int M, ScreenArgs sc, float* __restrict__ probe_rows) {
+// POOL: the pooled replay (screen_pool_store) - k_stn3d_pair_sp / k_stnkd_pair_sp
+template <bool POOL>
+__device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* __restrict__ W1,
+                                                  const float* __restrict__ b1, const f32x4* __restrict__ wp2,
+                                                  const float* __restrict__ b2, const f32x4* __restrict__ wp3,
+                                                  const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
+                                                  int M, const ScreenArgs& sc, float* __restrict__ probe_rows) {
   __shared__ __attribute__((aligned(16))) float smem[2 * TP * LD64 + 2 * TP * LD128];
   float* a1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
   float* a2 = smem + 2 * TP * LD64;   // [128][132]
@@ -535,16 +762,28 @@ __global__ __launch_bounds__(256) void k_stn3d_pair_s(catre_points P, const floa
     store_tile_lds_pre<1, 4, true, false>(acc, a2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<1>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
+  stn_conv3_screened<1, POOL>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
 }
+#define STN3D_PAIR_S_(NAME, POOL)                                                                                          \
+  __global__ __launch_bounds__(256) void NAME(catre_points P, const float* __restrict__ W1, const float* __restrict__ b1, \
+                                              const f32x4* __restrict__ wp2, const float* __restrict__ b2,                \
+                                              const f32x4* __restrict__ wp3, const float* __restrict__ b3,                \
+                                              float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,                 \
+                                              float* __restrict__ probe_rows) {                                           \
+    stn3d_pair_s_body<POOL>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows);                                    \
+  }
+STN3D_PAIR_S_(k_stn3d_pair_s, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp, true)
+#undef STN3D_PAIR_S_
 
-__global__ __launch_bounds__(256) void k_stnkd_pair_s(catre_points P, const float* __restrict__ trans3,
-                                                      const float* __restrict__ Wc1, const float* __restrict__ bc1,
-                                                      const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
-                                                      const f32x4* __restrict__ wpf2, const float* __restrict__ bf2,
-                                                      const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,
-                                                      float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,
-                                                      float* __restrict__ probe_rows) {
+template <bool POOL>
+__device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* __restrict__ trans3,
+                                                  const float* __restrict__ Wc1, const float* __restrict__ bc1,
+                                                  const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
+                                                  const f32x4* __restrict__ wpf2, const float* __restrict__ bf2,
+                                                  const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,
+                                                  float* __restrict__ pm, int B, int N, int M, const ScreenArgs& sc,
+                                                  float* __restrict__ probe_rows) {
   __shared__ __attribute__((aligned(16))) float smem[4 * TP * LD64 + 2 * TP * LD128];
   float* h1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
   float* f1 = smem + 2 * TP * LD64;   // [128][68]
@@ -587,5 +826,16 @@ __global__ __launch_bounds__(256) void k_stnkd_pair_s(catre_points P, const floa
     store_tile_lds_pre<1, 4, true, false>(acc, f2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<2>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
+  stn_conv3_screened<2, POOL>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
 }
+#define STNKD_PAIR_S_(NAME, POOL)                                                                                      \
+  __global__ __launch_bounds__(256) void NAME(                                                                        \
+      catre_points P, const float* __restrict__ trans3, const float* __restrict__ Wc1, const float* __restrict__ bc1, \
+      const f32x4* __restrict__ wpf1, const float* __restrict__ bf1, const f32x4* __restrict__ wpf2,                  \
+      const float* __restrict__ bf2, const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,                   \
+      float* __restrict__ pm, int B, int N, int M, ScreenArgs sc, float* __restrict__ probe_rows) {                   \
+    stnkd_pair_s_body<POOL>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows);       \
+  }
+STNKD_PAIR_S_(k_stnkd_pair_s, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp, true)
+#undef STNKD_PAIR_S_

@@ -273,7 +273,7 @@ def bump_param_epoch():
     _param_epoch[0] += 1
 
 
-FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6}
+FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7}
 
 
 def form_switch(name, value=None):

@@ -310,16 +310,20 @@ int catre_profile_enable(int kernel_id, int max_records);
  * error bound cannot rule a point out, k_trunk4s - same bits for FINITE activations; where the dense form returns Inf / NaN
  * this one may return another value, 6: the same screen for conv3 of the two STNs on the full-grid pair kernels,
  * k_stn3d_pair_s / k_stnkd_pair_s - it refines 5: the STN kernels are screened only while 5 and 6 are both on, so switch 5
- * off turns every screened form off; the caveat about non-finite activations covers the STN layers too),
+ * off turns every screened form off; the caveat about non-finite activations covers the STN layers too,
+ * 7: the screened kernels replay their candidates from ONE list per wave (all 256 channels of the wave, rounds of 64
+ * entries) instead of per-channel trips sized by the worst channel of a 32-channel block, k_trunk4sp - same bits as 5; it
+ * refines 5 and has no effect while 5 is off; catre_trunk_screen_probe follows it),
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
- * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2, 5 and 6 on, 3 and 4 off -
+ * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-7 on, 3 and 4 off -
  * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
- * CATRE_SCREEN_STN = 0,
+ * CATRE_SCREEN_STN / CATRE_SCREEN_POOL = 0,
  * CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
  * launched with. */
 int catre_form_switch(int id, int value);
 /* Experiment knobs of the instrumented library (id 0: start offset in cycles between the co-resident workgroups of the
- * STN kernels' first dispatch round); CATRE_ERR_UNSUPPORTED in the product library. */
+ * STN kernels' first dispatch round, id 2: the screened kernels' counters of catre_debug_screen_counts on (1, default) / off
+ * (0) - their atomics distort the phase stamps); CATRE_ERR_UNSUPPORTED in the product library. */
 int catre_debug_knob(int id, int value);
 /* Wait for the recorded events, write per-launch durations (ms) and reset the record counter. */
 int catre_profile_collect(float* ms_out, int max_out, int* n_out);
@@ -330,7 +334,9 @@ int catre_debug_trunk_trace(void* device_buffer);
 /* Instrumented library only (CATRE_ERR_UNSUPPORTED in the product): the screened forms' counters since the last reset,
  * three rows of 64 (trunk conv4, stn.conv3, fstn.conv3) -
  * row[0..31] candidates per (tile, channel) (31: >= 31), [32..47] replay trips per (wave, tile, m-block) (47: >= 15),
- * [48] (wave, tile) units in which an m-block needed more than one round of 4 trips, [49] all units. */
+ * [48] (wave, tile) units in which an m-block needed more than one round of 4 trips, [49] all units.
+ * With switch 7 on: [32..47] rounds of 64 list entries per (wave, tile), [48] units whose list filled up and was replayed
+ * in more than one batch, [50] sum of list entries, [51] sum of rounds. */
 int catre_debug_screen_counts(unsigned long long* out192, int reset);
 
 /* Identity of the stream capture `stream` is currently recording into (hipStreamGetCaptureInfo; 0 when the stream is not

@@ -1,5 +1,7 @@
 """Candidate-count histograms and further-rounds shares of the three screened layers (kernel-form switches `screen` and
-`screen_stn`: trunk conv4, stn.conv3, fstn.conv3) on the bench inputs.
+`screen_stn`: trunk conv4, stn.conv3, fstn.conv3) on the bench inputs.  With `screen_pool` on (the default; CATRE_SCREEN_POOL=0
+for the per-channel replay) the kernels that replay from one list per wave report list entries and rounds of 64 per
+(wave, tile) instead of trips per 32-channel block.
 
 Needs the instrumented library (`make -C catre_amd/csrc TRACE=1`), whose screened kernels count while they run:
     CATRE_HIP_LIB=catre_amd/csrc/libcatre_hip_trace.so python profiles/screen_candidates.py [out.txt]
@@ -32,9 +34,14 @@ hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts (nee
 model.refine(batch, n_iter=K)
 torch.cuda.synchronize()
 hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts")
-lines = [f"B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights; replay chains a lane carries at once: 4"]
+pool = hip.form_switch("screen_pool")
+lines = [f"B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights; screen_pool {'on' if pool else 'off'}; "
+         "per-channel replay: chains a lane carries at once: 4"]
 for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_s)", "fstn.conv3 (k_stnkd_pair_s)")):
     c = list(cnt)[64 * row:64 * row + 64]
+    pooled = c[51] > 0   # only the pooled replay counts rounds
+    if pooled:
+        name = name.replace("_s)", "_sp)").replace("k_trunk4s", "k_trunk4sp")
     lines.append(f"screened {name}")
     tot = sum(c[:32])
     mean = sum(i * v for i, v in enumerate(c[:32])) / max(tot, 1)
@@ -42,6 +49,14 @@ for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_
     for i, v in enumerate(c[:32]):
         if v:
             lines.append(f"  {i:2d}: {v:10d}  {v / tot:.6f}")
+    if pooled:
+        lines.append(f"list entries per (wave, tile): mean {c[50] / max(c[49], 1):.2f}; rounds of 64 entries: mean "
+                     f"{c[51] / max(c[49], 1):.4f} over {c[49]} units (bin 15 = 15 and more)")
+        for i, v in enumerate(c[32:48]):
+            if v:
+                lines.append(f"  {i:2d}: {v:10d}  {v / max(c[49], 1):.6f}")
+        lines.append(f"(wave, tile) units whose list filled up (replayed in more than one batch): {c[48]} of {c[49]}")
+        continue
     tt = sum(c[32:48])
     tmean = sum(i * v for i, v in enumerate(c[32:48])) / max(tt, 1)
     lines.append(f"replay trips per (wave, tile, 32-channel block): {tt} blocks, mean {tmean:.4f} (bin 15 = 15 and more)")

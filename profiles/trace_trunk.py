@@ -13,6 +13,7 @@ model.refine(batch, n_iter=1)
 tiles = B*32
 # the rotation-head kernels of the instrumented build stamp at offset 1 << 24 of the same buffer
 buf = torch.zeros((1 << 24) + tiles*8*16, dtype=torch.int64, device='cuda')
+hip.load().catre_debug_knob(2, 0)  # the screened kernels' counters off: their atomics would dominate the last phase
 hip.load().catre_debug_trunk_trace(ctypes.c_void_p(buf.data_ptr()))
 model.refine(batch, n_iter=1)
 torch.cuda.synchronize()
