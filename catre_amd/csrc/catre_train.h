@@ -1614,7 +1614,9 @@ __global__ __launch_bounds__(256) void k_maxlin_bwd_w(const float* __restrict__ 
 // partial sums are merged through LDS in lane order (deterministic).  The walk above is one chain of C / 8 steps of two
 // dependent global round trips whatever K is (150 us for K = 128 as for K = 512); here it is C / (8 CL) steps.
 // rowpos != nullptr: X holds COMPACT rows (the live rows of a row-sparse chain, recomputed by k_stn_recompute) - dense row r
-// sits at rowpos[r]; an arg-max row with dg == 0 is not live (rowpos < 0) and is read as row 0 (its product is an exact zero).
+// sits at rowpos[r]; an arg-max row with dg == 0 is not live (rowpos < 0): its operand is taken as zero (selected after the
+// load of compact row 0, which keeps the address in bounds - with no live row at all that row was never written, and
+// 0 * garbage is NaN whenever the garbage is), so its product is an exact zero and every other sum keeps its bits.
 template <bool XH = false>  // XH: X holds bf16 rows (ldx in elements)
 __global__ __launch_bounds__(256) void k_maxlin_bwd_w4(const float* __restrict__ dg, const int* __restrict__ idx,
                                                        const float* __restrict__ X, int ldx, float* __restrict__ dW,
@@ -1635,15 +1637,24 @@ __global__ __launch_bounds__(256) void k_maxlin_bwd_w4(const float* __restrict__
         g[u] = c < C ? dg[(size_t)cc * J + j] : 0.f;
         row[u] = idx[(size_t)cc * J + j];
       }
+      bool dead[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) dead[u] = false;
       if (rowpos) {
 #pragma unroll
-        for (int u = 0; u < 8; ++u) row[u] = max(rowpos[row[u]], 0);
+        for (int u = 0; u < 8; ++u) {
+          const int p = rowpos[row[u]];
+          dead[u] = p < 0;
+          row[u] = max(p, 0);
+        }
       }
       f32x4 xv[8];
+      const f32x4 z = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
         if constexpr (XH) xv[u] = ld_bf4(X, ((size_t)row[u] * ldx >> 2) + q);
         else xv[u] = *reinterpret_cast<const f32x4*>(X + (size_t)row[u] * ldx + 4 * q);
+        xv[u] = dead[u] ? z : xv[u];
       }
 #pragma unroll
       for (int u = 0; u < 8; ++u) {
