@@ -5,6 +5,8 @@
 #include <cstdlib>
 #include <atomic>
 #include <mutex>
+#include <cstring>
+#include <vector>
 
 #include "catre_device.h"
 
@@ -1599,6 +1601,7 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 #include "catre_heads.h"
 #include "catre_aug.h"
 #include "catre_pcl.h"
+#include "catre_pclf.h"
 #include "catre_loss.h"
 #include "catre_eval.h"
 
@@ -3029,6 +3032,8 @@ int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, si
                      ws + L.total, N, scratch, slot_cap, sample_idx_out);
   return check_launch();
 }
+
+#include "catre_pclf_api.inc"
 
 // ---- row f1: training loss ---------------------------------------------------------------------------------
 // One implementation behind both generations of entry points: nl loss slots (LOSS_NL: losses[6 + 14], part rows of

@@ -230,6 +230,11 @@ _SIGS = {
     "catre_pcl_candidates": (_I, [_P, _P, _P, _P, _P, ctypes.c_float, _I, _I, _I, _I, _P, _SZ, _P, _P]),
     "catre_pcl_sample": (_I, [_P, _P, _P, _SZ, _P, ctypes.c_uint64, _I, _I, _I, _I, _P, _P, _P]),
     "catre_pcl_fps": (_I, [_P, _P, _P, _SZ, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "catre_pclf_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "catre_pclf_candidates": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, ctypes.c_float, _I, _I, _I, _I, _I, _P, _SZ, _P, _P]),
+    "catre_pclf_sample": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
+    "catre_pclf_fps": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
+    "catre_depth_augment": (_I, [_P, _I, ctypes.c_float, _P, _I, _P, _P, _P, ctypes.c_uint64, _P, _I, _I, _I, _P]),
     "catre_loss_fwd": (_I, [_P] * 15 + [_I, _I, _I, _P]),
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),

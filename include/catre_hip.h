@@ -797,6 +797,67 @@ int catre_pcl_sample(const float* depth, const float* K9, const void* workspace,
 int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, size_t ws_bytes, int I, int H, int W, int N,
                   float* scratch, int slot_cap, long long* sample_idx_out, void* stream);
 
+/* ---- row f3 for a data batch: I instances spread over F depth maps, all frames at once ------------------- */
+
+/* The three entry points above with a frame per instance.  depth [F,H,W] fp32 metres (device); K = HOST [F][9]
+ * intrinsics, row-major, one per frame; frame_of = HOST [I], the frame of every instance (any order).  The pixels of
+ * instance i are either masks[i] != 0 (masks [I,H,W] bytes, device, may be NULL = the whole frame) or
+ * labels[frame_of[i]][pix] == label_of[i]: labels [F,H,W] on the device with label_bytes = 1 (uint8) or 4 (int32),
+ * one label image per frame, label_of = HOST [I].  Giving both masks and labels is an error.
+ * Every entry point checks its host arrays before anything is launched - 0 <= frame_of[i] < F, fx and fy of every
+ * frame non-zero, H * W < 2^30, I <= 65535 - and returns CATRE_ERR_BAD_ARG otherwise, so no index it did not check
+ * reaches a kernel; it then stages them to the head of `workspace` with one hipMemcpyAsync on `stream` (from pageable
+ * memory: the host arrays may be reused when the call returns, the call waits for that copy, and it cannot be captured
+ * into a graph).  Per frame the arithmetic is that of the single-frame kernels - the same
+ * device functions on the frame's depth map and camera - so a frame gives the bits catre_pcl_* give for it alone.
+ * catre_pclf_workspace_bytes: >= catre_pcl_workspace_bytes(I, H, W), growing with I; 0 for F, I, H or W <= 0 and for
+ * H * W >= 2^30.  counts_out [I] (device, optional) as above. */
+size_t catre_pclf_workspace_bytes(int F, int I, int H, int W);
+int catre_pclf_candidates(const float* depth, const float* K, const int32_t* frame_of, const unsigned char* masks,
+                          const void* labels, int label_bytes, const int32_t* label_of, const float* poses,
+                          const float* scales, float ratio, int use_ball, int F, int I, int H, int W, void* workspace,
+                          size_t ws_bytes, int32_t* counts_out, void* stream);
+
+/* catre_pcl_sample for the lists catre_pclf_candidates left in `workspace`.  sample_idx [I,N] (device) as there, or
+ * NULL: the keyed permutation, keyed by (seeds[frame_of[i]], rank of instance i within its frame), seeds = HOST [F] -
+ * a frame gets the cloud catre_pcl_sample gives it alone under that seed, whatever else is in the batch.  rank_of =
+ * HOST [I] or NULL (the rank is then counted in the order given; a caller that splits a batch into several calls
+ * passes the ranks of the whole batch).  pix_out [I,N] (optional): pixel index inside the instance's frame.  Instances
+ * without any candidate produce zeros and pix -1. */
+int catre_pclf_sample(const float* depth, const float* K, const int32_t* frame_of, const int32_t* rank_of,
+                      void* workspace, size_t ws_bytes, const long long* sample_idx, const unsigned long long* seeds,
+                      int F, int I, int H, int W, int N, float* pcl_out, int32_t* pix_out, void* stream);
+/* catre_pcl_fps for the lists catre_pclf_candidates left in `workspace` (scratch, slot_cap: as there). */
+int catre_pclf_fps(const float* depth, const float* K, const int32_t* frame_of, void* workspace, size_t ws_bytes, int F,
+                   int I, int H, int W, int N, float* scratch, int slot_cap, long long* sample_idx_out, void* stream);
+
+/* INPUT.AUG_DEPTH: the loader's depth augmentation (core/catre/datasets/data_loader.py:530-543,
+ * core/utils/depth_aug.py:5-23) of F depth maps in one pass, in the loader's order:
+ *   fill   depth == 0 -> a draw from N(0, 0.1) (the median the reference adds is that of a set of zeros); a negative
+ *          fill stays and fails the `depth > 0` test of the sampling, as in the reference
+ *   drop   depth *= (u > drop_ratio), u ~ U(0,1)
+ *   noise  where depth > 0 after both: depth += noise_level * g, g ~ N(0,1)
+ * depth_in [F,H,W]: fp32 metres, or uint16 (in_is_u16) converted as (float)v / depth_div with an IEEE division
+ * (= depth.astype("float32") / 1000.0 bit for bit); depth_out [F,H,W] fp32, may be depth_in for fp32 input.
+ * frames [F] (DEVICE): per frame which steps run (CATRE_DAUG_* flags), drop_ratio, noise_level and a 64-bit key.
+ * use_draws != 0: draw_fill / draw_keep / draw_gauss [F,H,W] float64 (device) hold the reference's draws at the pixels
+ *   that consume one; a NULL array turns its step off.  The arithmetic is numpy's (float64 where numpy promotes, one
+ *   rounding to fp32): bit-identical to the reference given its draws.
+ * use_draws == 0: Philox4x32-10 at (seed, frames[f].key, pixel, step), Box-Muller normals, fp32 arithmetic - equally
+ *   distributed, a different stream.  A frame's result depends on (seed, key) only: not on F, not on its slot.
+ * F <= 65535, H * W < 2^30. */
+#define CATRE_DAUG_FILL 1
+#define CATRE_DAUG_DROP 2
+#define CATRE_DAUG_NOISE 4
+typedef struct catre_depth_aug_frame {
+  double drop_ratio, noise_level;
+  uint64_t key;
+  int32_t flags, reserved;
+} catre_depth_aug_frame;
+int catre_depth_augment(const void* depth_in, int in_is_u16, float depth_div, const catre_depth_aug_frame* frames,
+                        int use_draws, const double* draw_fill, const double* draw_keep, const double* draw_gauss,
+                        unsigned long long seed, float* depth_out, int F, int H, int W, void* stream);
+
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
