@@ -837,7 +837,8 @@ __device__ __forceinline__ void trunk4_body(float* smem, catre_points P, const f
                                             const float* __restrict__ b3, const f32x4* __restrict__ wp4,
                                             const float* __restrict__ b4, float* __restrict__ pm,
                                             float* __restrict__ pointfeat, int B, int N, int M,
-                                            unsigned long long* __restrict__ trace, const TrainSave& sv, Tail& tl) {
+                                            unsigned long long* __restrict__ trace, const TrainSave& sv, Tail& tl,
+                                            const int tile, const int tid) {
 #define TRUNK_STAMP(i)                                                                     \
   do {                                                                                     \
     if (CATRE_TRACE_ON && trace && lane == 0) trace[((size_t)tile * 8 + wave) * 8 + (i)] = __builtin_readcyclecounter(); \
@@ -847,9 +848,9 @@ __device__ __forceinline__ void trunk4_body(float* smem, catre_points P, const f
   float* pf = smem + TP * LD64 + 4096;   // [64][68]
   float* a3 = smem;                      // [64][512] swizzled
   float* a2 = smem + TP * 512;           // [64][128] swizzled
-  const int tid = threadIdx.x, lane = tid & 63;
+  // (tile, tid): blockIdx.x and threadIdx.x of the one-tile kernels; the run form (k_trunk4sr) walks several tiles
+  const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int tile = blockIdx.x;
   const TileInfo ti = tile_info(tile, B, N, M);
   const bool ft = trans64 != nullptr;
   TRUNK_STAMP(0);
@@ -984,7 +985,8 @@ __global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __r
                                                 unsigned long long* __restrict__ trace, TrainSave sv = TrainSave{}) {
   __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
   Trunk4Dense<SAVE> tl;
-  trunk4_body<SAVE>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace, sv, tl);
+  trunk4_body<SAVE>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace, sv, tl,
+                    blockIdx.x, threadIdx.x);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1696,7 +1698,7 @@ PackLayout pack_layout(int ts_in) {
 
 struct WsLayout {
   size_t tspart, xbuf, kbuf, pm, pool, h1, h2, trans3, trans64, gfeat, pointfeat, dt, ds, rot6d, bias0, gn0, gn1, aff0, gn1stat, y1, rpart,
-      bar, total;  // offsets in floats
+      bar, frun, total;  // offsets in floats
 };
 
 WsLayout ws_layout(int B, int N, int M) {
@@ -1735,6 +1737,8 @@ WsLayout ws_layout(int B, int N, int M) {
   }
   L.rpart = take(b * 2 * T * 4);
   L.bar = take(64);  // k_fc_tail's barrier counters
+  // k_trunk4sr: 1024 running maxima per run; the most runs a grid can have is at run length 2
+  L.frun = take(b * ((TN + 1) / 2 + (TM + 1) / 2) * 1024);
   L.total = o;
   return L;
 }
@@ -1835,11 +1839,13 @@ static int bf_pair_min() {
 // per K = 4 refine at B = 256, profiles/screen_ab.jsonl), the screened conv3 max-pool of the STN pair kernels
 // (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl), the
 // pooled replay of the screened kernels (k_trunk4sp / k_stn*_pair_sp, only together with the screens they refine) ON (24.55 vs
-// 28.70 ms, profiles/screen_pool_ab.jsonl); the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
-// CATRE_SCREEN_STN / CATRE_SCREEN_POOL = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
+// 28.70 ms, profiles/screen_pool_ab.jsonl), the pooled kernels on runs of tiles with a carried running maximum (k_trunk4sr /
+// k_stn*_pair_sr, only together with the pooled replay they refine) ON (21.59 vs 24.25 ms, profiles/screen_run_ab.jsonl);
+// the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
+// CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
 // sets the process default once, catre_form_switch changes it at run time.
 enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64,
-       FORM_SCREEN_POOL = 128 };
+       FORM_SCREEN_POOL = 128, FORM_SCREEN_RUN = 256 };
 #ifndef CATRE_SCREEN_DEFAULT
 #define CATRE_SCREEN_DEFAULT true
 #endif
@@ -1848,6 +1854,9 @@ enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC
 #endif
 #ifndef CATRE_SCREEN_POOL_DEFAULT
 #define CATRE_SCREEN_POOL_DEFAULT true
+#endif
+#ifndef CATRE_SCREEN_RUN_DEFAULT
+#define CATRE_SCREEN_RUN_DEFAULT true
 #endif
 static std::atomic<int> g_forms{-1};
 static int forms() {
@@ -1861,7 +1870,8 @@ static int forms() {
         (on("CATRE_STN_PAIR") ? FORM_STN_PAIR : 0) | (on("CATRE_ROTW", false) ? FORM_ROTW : 0) |
         (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0) |
         (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0) |
-        (on("CATRE_SCREEN_POOL", CATRE_SCREEN_POOL_DEFAULT) ? FORM_SCREEN_POOL : 0);
+        (on("CATRE_SCREEN_POOL", CATRE_SCREEN_POOL_DEFAULT) ? FORM_SCREEN_POOL : 0) |
+        (on("CATRE_SCREEN_RUN", CATRE_SCREEN_RUN_DEFAULT) ? FORM_SCREEN_RUN : 0);
     g_forms.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -1876,6 +1886,35 @@ static bool screen_on() { return forms() & FORM_SCREEN; }  // fp32 full grids: c
 static bool screen_stn_on() { return (forms() & (FORM_SCREEN | FORM_SCREEN_STN)) == (FORM_SCREEN | FORM_SCREEN_STN); }
 // the screened kernels replay their candidates from one list per wave (k_trunk4sp); refines `screen`
 static bool screen_pool_on() { return forms() & FORM_SCREEN_POOL; }
+// the pooled trunk walks runs of tiles of one cloud and carries the running maximum (k_trunk4sr); refines `screen_pool`
+static bool screen_run_on() { return (forms() & (FORM_SCREEN_POOL | FORM_SCREEN_RUN)) == (FORM_SCREEN_POOL | FORM_SCREEN_RUN); }
+// Run length of k_trunk4sr.  One workgroup fits a CU, so a grid of R workgroups that each walk up to S tiles takes
+// ceil(R / cus) * S tile slots.  The rule: the largest S <= 16 that takes no more slots than the one-tile grid's
+// ceil(tiles / cus) - its last round is then as full as the one-tile grid's - else 1, the one-tile kernel k_trunk4sp.
+// (B = 256, N = M = 1024 on 256 CUs: 16; B = 128: 16; B = 64: 8; B = 200: 1.)
+static std::atomic<int> g_run_len{0};  // catre_screen_run_len: > 0 forces the length
+static int screen_run_rule(int B, int N, int M, int cus) {
+  const int TN = (N + TP - 1) / TP, TM = (M + TP - 1) / TP;
+  const long long slots1 = ((long long)B * (TN + TM) + cus - 1) / cus;
+  for (int S = 16; S > 1; --S) {
+    const long long R = (long long)B * ((TN + S - 1) / S + (TM + S - 1) / S);
+    if ((R + cus - 1) / cus * S <= slots1) return S;
+  }
+  return 1;
+}
+static int device_cus() {
+  static const int n = [] {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0)
+      v = 256;
+    return v;
+  }();
+  return n;
+}
+static int screen_run_len(int B, int N, int M) {
+  const int f = g_run_len.load(std::memory_order_relaxed);
+  return f > 0 ? f : screen_run_rule(B, N, M, device_cus());
+}
 // ... and the STN pair kernels (k_stn*_pair_sp): with `screen_stn` as well.  Its own default so that the two kernel families
 // can follow their own A/B (CATRE_SCREEN_POOL_STN_DEFAULT)
 #ifndef CATRE_SCREEN_POOL_STN_DEFAULT
@@ -1884,6 +1923,18 @@ static bool screen_pool_on() { return forms() & FORM_SCREEN_POOL; }
 static bool screen_pool_stn_on() {
   static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_POOL_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_POOL_STN_DEFAULT; }();
   return screen_pool_on() && stn;
+}
+// ... and the pooled STN pair kernels as k_stn*_pair_sr, runs of S / 2 pairs.  Its own default so that the two kernel
+// families can follow their own A/B (CATRE_SCREEN_RUN_STN_DEFAULT)
+#ifndef CATRE_SCREEN_RUN_STN_DEFAULT
+#define CATRE_SCREEN_RUN_STN_DEFAULT true
+#endif
+static bool screen_run_stn_on() {
+  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_RUN_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_RUN_STN_DEFAULT; }();
+  return screen_run_on() && screen_stn_on() && screen_pool_stn_on() && stn;
+}
+inline int stn_pair_runs(int B, int N, int M, int SP) {
+  return B * ((((N + TP - 1) / TP + 1) / 2 + SP - 1) / SP + (((M + TP - 1) / TP + 1) / 2 + SP - 1) / SP);
 }
 static bool rotw_on() { return forms() & FORM_ROTW; }  // rotation heads, one wave per SIMD (k_rot_l1w); off (default): k_rot_l1<1>
 
@@ -1935,6 +1986,12 @@ void launch_stn3d(const catre_points* pts, const float* const* prm, const float*
                      pkb(packed, L.sp_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
+  } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
+    const int SP = S / 2;
+    hipLaunchKernelGGL(k_stn3d_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
+                       Stn3dRunArgs{*pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2),
+                                    prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm,
+                                    pkb(packed, L.scr_stn_c3), packed + L.scr_nw_stn, B, N, M, SP});
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
     hipLaunchKernelGGL(screen_pool_stn_on() ? k_stn3d_pair_sp : k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
                        prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
@@ -1973,6 +2030,13 @@ void launch_stnkd(const catre_points* pts, const float* trans3, const float* con
                      prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
+  } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
+    const int SP = S / 2;
+    hipLaunchKernelGGL(k_stnkd_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
+                       StnkdRunArgs{*pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1),
+                                    prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2), prm[CATRE_P_FSTN_CONV2_B],
+                                    pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm,
+                                    pkb(packed, L.scr_fstn_c3), packed + L.scr_nw_fstn, B, N, M, SP});
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
     hipLaunchKernelGGL(screen_pool_stn_on() ? k_stnkd_pair_sp : k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
                        prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
@@ -2013,6 +2077,15 @@ void launch_trunk(const catre_points* pts, const float* trans3, const float* tra
                      ws + W.pm, pointfeat, B, N, M, g_trunk_trace)
     RS_DISPATCH(row_split(tiles), LAUNCH_)
 #undef LAUNCH_
+  } else if (const int S = row_split8(tiles) == 1 && trunk4_on() && screen_on() && screen_run_on() ? screen_run_len(B, N, M) : 1;
+             S > 1) {
+    const int runs = B * (((N + TP - 1) / TP + S - 1) / S + ((M + TP - 1) / TP + S - 1) / S);
+    hipLaunchKernelGGL(k_trunk4sr, dim3(runs), dim3(256), 0, st,
+                       TrunkRunArgs{*pts, trans3, trans64, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2),
+                                    prm[CATRE_P_CONV2_B], pk4(packed, L.c3), prm[CATRE_P_CONV3_B], pk4(packed, L.c4),
+                                    prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, g_trunk_trace,
+                                    ScreenArgs{pkb(packed, L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps}, ws + W.frun,
+                                    B, N, M, S});
   } else if (row_split8(tiles) == 1 && trunk4_on() && (screen_on() || probe_s)) {
     hipLaunchKernelGGL(screen_pool_on() ? k_trunk4sp : k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64,
                        prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
@@ -2831,11 +2904,22 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 7) return -1;
+  if (id < 0 || id > 8) return -1;
   const int bit = 1 << id;
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);
   return (cur & bit) ? 1 : 0;
+}
+
+int catre_screen_run_len(int value) {
+  const int prev = g_run_len.load(std::memory_order_relaxed);
+  if (value >= 0) g_run_len.store(value > 16 ? 16 : value, std::memory_order_relaxed);
+  return prev;
+}
+
+int catre_screen_run_rule(int B, int N, int M, int cus) {
+  if (B <= 0 || N <= 0 || M < 0 || cus <= 0) return -1;
+  return screen_run_rule(B, N, M, cus);
 }
 
 int catre_debug_knob(int id, int value) {

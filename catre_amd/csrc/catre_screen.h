@@ -35,6 +35,16 @@
 // copies of the last valid point (load_point clamps) - identical S and eps - and are dropped from the candidate set.
 // The tile maximum is fmaxf over the candidates' replayed Y, then bias exactly as max_tile_store_pre.
 //
+// Run form (kernel-form switch `screen_run`, k_trunk4sr): one workgroup walks consecutive tiles of ONE cloud and carries
+// F_c, the exact pre-bias maximum of channel c over the tiles it has finished (-inf before the first).  Tile t selects with
+// L = max(F_c, max_p fl(S - eps)), candidates fl(S + eps) >= L.  A dropped point has Y <= fl(S + eps) < L (the roundings are
+// inside eps's inflation, as above) and L <= max(F_c, max_p Y): it is not the maximum of the run so far, and
+// max(F_c, max over the candidates' Y) is that maximum exactly.  A point that TIES with F_c stays a candidate
+// (>=), so the all-ties worst case keeps its size.  The candidate set may now be empty (every point of the tile below
+// F_c); the m64 == 0 -> 1 guard remains for the first tile of a run only, where F_c = -inf and only NaN inputs empty it.
+// pm[tile] receives fl(F_c + b_c) after the tile: fl(x + b) is monotone in x, so the maximum over a cloud's rows is the
+// same float the per-tile maxima give.
+//
 // Replay: GemmPipe::run feeds output (channel c, point p) the products in the order  kc = 0 .. K/8-1, s = 0 .. 3:
 // k = 8 kc + s, then k = 8 kc + 4 + s, starting from 0 - as fmaf (profiles/experiments/screen_mfma_chain.md).
 #pragma once
@@ -78,7 +88,7 @@ struct ScreenArgs {
 // diagnostic build, one row per screened layer (0 trunk conv4, 1 stn conv3, 2 fstn conv3): [0..31] candidates per
 // (tile, channel) (31: >= 31), [32..47] trips per (wave, tile, m-block) (47: >= 15), [48] (wave, tile) units with an
 // m-block of more than SCREEN_CMAX trips, [49] all units.  Pooled form: [32..47] rounds of 64 entries per (wave, tile),
-// [48] units that needed more than one batch, [50] sum of entries, [51] sum of rounds
+// [48] units that needed more than one batch, [50] sum of entries, [51] sum of rounds, [52] units with an empty list (run form)
 __device__ unsigned long long g_screen_cnt[3][64];
 // counting on / off (catre_debug_knob 2): the counters' atomics cost far more than the epilogue they count in, so the
 // phase stamps of profiles/trace_trunk.py are taken with them off
@@ -90,6 +100,14 @@ __device__ int g_screen_count_on = 1;
 #endif
 
 #define SCREEN_CMAX 4  // replay chains a lane carries at once; an m-block that needs more trips takes further rounds
+
+// Lane exchanges with the caller's OWN lane id: __shfl_xor / __shfl_up / __shfl compute the lane id themselves, a value the
+// compiler hoists out of k_trunk4sr's loop over tiles - and then it is live across the 256-accumulator sweep and spills.
+// (`lane` may carry higher bits, e.g. a thread id: ds_bpermute takes the address modulo the wave.)
+template <class T>
+__device__ __forceinline__ T lane_get(T v, int src_lane) {
+  return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
+}
 
 // Row addressing of the fp32 LDS image a screened layer reads: SWZ = the XOR-swizzled [rows][C] image of the trunk (pitch
 // C, chunk c of row r at c ^ (r & 15)), otherwise a padded image of pitch `ld` (the STN kernels' [128][LD128]).
@@ -111,7 +129,7 @@ __device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, 
     s = fmaf(v[3], v[3], s);
   }
 #pragma unroll
-  for (int o = 1; o < PER; o <<= 1) s += __shfl_xor(s, o);
+  for (int o = 1; o < PER; o <<= 1) s += lane_get(s, tid ^ o);
   if (part == 0) na[row] = fmaf(sqrtf(s), 1.f + 0x1p-12f, 0x1p-58f);
 }
 
@@ -372,12 +390,22 @@ __device__ __forceinline__ void screen_replay_pool(const f32x4* __restrict__ wba
 // index 32 mb + n).  Lane l owns channels 4 l .. 4 l + 3: counts, list offsets (exclusive prefix in channel order), the scan
 // of the results and the store.  A batch is the longest run of whole channels from `start` whose entries fit the list:
 // one batch on all but tie-heavy tiles, at most 32 (every channel has <= 64 entries, so a batch holds >= 8 channels).
-template <int K, bool SWZ, int LAYER>
+// RUN: frun[0 .. 1024) is the run's running maximum (pre-bias, the `best` of the tiles before this one; not read when
+// `first`): `best` starts from it and is written back.  The list may then be empty and the replay loop is skipped.
+template <int K, bool SWZ, int LAYER, bool RUN = false>
 __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbase, const float* x, int ld,
                                                   unsigned long long* sets, float* __restrict__ out,
-                                                  const float* __restrict__ bias, int ch0, bool relu, int lane) {
+                                                  const float* __restrict__ bias, int ch0, bool relu, int lane,
+                                                  float* frun = nullptr, bool first = true) {
   unsigned* list = reinterpret_cast<unsigned*>(sets + 256);
   float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  if constexpr (RUN) {
+    if (!first) {
+      const f32x4 f = *reinterpret_cast<const f32x4*>(frun + ch0 + 4 * lane);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) best[j] = f[j];
+    }
+  }
 #ifdef CATRE_DEBUG_TRACE
   int entries = 0, rounds = 0, batches = 0;
 #endif
@@ -393,7 +421,7 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     int incl = s;
 #pragma unroll
     for (int o = 1; o < 64; o <<= 1) {
-      const int t = __shfl_up(incl, o);
+      const int t = lane_get(incl, lane - o);
       if (lane >= o) incl += t;
     }
     // channels whose inclusive prefix fits: a prefix [0, end) of the channels (those below `start` count 0 entries)
@@ -406,7 +434,7 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
       end += __popcll(__ballot(run <= SCREEN_POOL_CAP));
     }
     const int sel = (end - 1) & 3;
-    const int total = __shfl(sel == 0 ? last[0] : sel == 1 ? last[1] : sel == 2 ? last[2] : last[3], (end - 1) >> 2);
+    const int total = lane_get(sel == 0 ? last[0] : sel == 1 ? last[1] : sel == 2 ? last[2] : last[3], (end - 1) >> 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int cw = 4 * lane + j;
@@ -447,6 +475,12 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
 #endif
     start = end;
   }
+  if constexpr (RUN) {
+    // read again by THIS wave only (other lanes of it), a tile later and behind the barriers between the tiles: the release
+    // at workgroup scope orders the store before them, the acquire in front of the reads is screen_select_store's
+    *reinterpret_cast<f32x4*>(frun + ch0 + 4 * lane) = f32x4{best[0], best[1], best[2], best[3]};
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+  }
   const f32x4 b = *reinterpret_cast<const f32x4*>(bias + ch0 + 4 * lane);
   f32x4 v;
 #pragma unroll
@@ -462,6 +496,7 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     SCREEN_COUNT(LAYER, 49, 1ull);
     SCREEN_COUNT(LAYER, 50, entries);
     SCREEN_COUNT(LAYER, 51, rounds);
+    if (entries == 0) SCREEN_COUNT(LAYER, 52, 1ull);
   }
 #endif
 }
@@ -476,12 +511,15 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
 //   LAYER: the row of g_screen_cnt the instrumented build counts into
 //   POOL : the candidates of the wave's MB * 32 = 256 channels are replayed from one list (screen_pool_store); the selection is
 //          the same, `sets` then holds one set per channel at [mb * 32 + n]
-template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false>
+//   RUN  : (POOL only) the run form: frun = the run's running maximum, see screen_pool_store and the header
+template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false, bool RUN = false>
 __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
                                                     const float* __restrict__ nw, const float* na, const float* x,
                                                     unsigned long long* sets, float* __restrict__ out,
                                                     const float* __restrict__ bias, int ch0, bool relu, int valid, int tile,
-                                                    const ScreenArgs& sc, int lane, int ld = K) {
+                                                    const ScreenArgs& sc, int lane, int ld = K, float* frun = nullptr,
+                                                    bool first = true) {
+  static_assert(POOL || !RUN, "the run form refines the pooled replay");
   constexpr int NKC8 = K / 64;
   const int n = lane & 31, h = lane >> 5;
   const int partner = (lane ^ 32) << 2;  // ds_bpermute address of the channel's other half-wave lane
@@ -502,12 +540,24 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
       for (int i = 0; i < 32; ++i)
         if ((i >> 4) * 32 + (i & 3) + 8 * ((i & 15) >> 2) + 4 * h < valid) vmask |= 1u << i;
     }
+    // run form: the running maxima of the lane's MB channels, requested together in front of the selection
+    float fc[RUN ? MB : 1];
+    if constexpr (RUN) {
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) fc[mb] = -INFINITY;
+      if (!first) {
+#pragma unroll
+        for (int mb = 0; mb < MB; ++mb) fc[mb] = frun[ch0 + mb * 32 + n];
+      }
+    }
     // candidates of the lane's channel as a 64-bit set: bit 32 h' + 16 nb + r, the same word in both half-waves
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
       float e1, e0;
       screen_eps_coef<K>(nw[ch0 + mb * 32 + n], e1, e0);
       float L = -INFINITY;
+      if constexpr (RUN) L = fc[mb];
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
@@ -532,7 +582,8 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
       }
       const unsigned other = swap32(own);
       unsigned long long m64 = h ? ((unsigned long long)own << 32) | other : ((unsigned long long)other << 32) | own;
-      if (m64 == 0) m64 = 1;  // NaN inputs only: keep the replay well defined
+      // NaN inputs only: keep the replay well defined (run form: empty is legal once the channel has a running maximum)
+      if (m64 == 0 && (!RUN || L == -INFINITY)) m64 = 1;
       if constexpr (POOL) {
 #ifdef CATRE_DEBUG_TRACE
         const int c = __popcll(m64);
@@ -548,7 +599,7 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
     static_assert(MB == 8, "lane l owns channels 4 l .. 4 l + 3 of the wave's 256");
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    screen_pool_store<K, SWZ, LAYER>(wf - n, x, ld, sets, out, bias, ch0, relu, lane);
+    screen_pool_store<K, SWZ, LAYER, RUN>(wf - n, x, ld, sets, out, bias, ch0, relu, lane, frun, first);
     return;
   }
 #ifdef CATRE_DEBUG_TRACE
@@ -616,9 +667,11 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
 // k_trunk4 with conv4 512 -> 1024 screened: conv1 .. conv3 and the a3 image are trunk4_body's; the last layer is the
 // split-bf16 screen over all 1024 x 64 outputs and the fp32 replay of the candidates.  Same bits as k_trunk4<false>.
 // ------------------------------------------------------------------------------------------
-template <bool POOL>
+template <bool POOL, bool RUN = false>
 struct Trunk4ScreenT {
   ScreenArgs sc;
+  float* frun;  // run form: the run's 1024 running maxima (workspace), and whether this is the run's first tile
+  bool first;
   const f32x4* wf;  // fp32 fragments of the wave's channels (the replay reads them), + (lane & 31)
   const float* b4;
   ScreenPipe8<2> g4;
@@ -643,8 +696,8 @@ struct Trunk4ScreenT {
     // the two) - the sweep above runs at exactly 256 VGPRs next to its 256 accumulators, and a lane id live across it is one
     // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-    screen_select_store<8, 512, true, 0, POOL>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32, false,
-                                               valid, tile, sc, lane);
+    screen_select_store<8, 512, true, 0, POOL, RUN>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
+                                                    false, valid, tile, sc, lane, 512, frun, first);
   }
 };
 typedef Trunk4ScreenT<false> Trunk4Screen;
@@ -661,7 +714,7 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
   Trunk4Screen tl;
   tl.sc = sc;
   trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
-                     TrainSave{}, tl);
+                     TrainSave{}, tl, blockIdx.x, threadIdx.x);
 }
 
 // the same kernel with the pooled replay (screen_pool_store)
@@ -677,7 +730,72 @@ __global__ __launch_bounds__(256) void k_trunk4sp(catre_points P, const float* _
   Trunk4ScreenT<true> tl;
   tl.sc = sc;
   trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
-                     TrainSave{}, tl);
+                     TrainSave{}, tl, blockIdx.x, threadIdx.x);
+}
+
+// Run -> tiles.  Runs are enumerated like tiles, observed clouds first; a cloud of T tiles has ceil(T / S) runs of S
+// consecutive tiles, the last one shorter.  No run crosses a cloud.
+__device__ __forceinline__ void run_info(int rid, int B, int N, int M, int S, int& tile0, int& nt) {
+  const int TN = (N + TP - 1) / TP, TM = (M + TP - 1) / TP;
+  const int RN = (TN + S - 1) / S, RM = (TM + S - 1) / S;
+  if (rid < B * RN) {
+    const int k = rid % RN;
+    tile0 = (rid / RN) * TN + k * S;
+    nt = min(S, TN - k * S);
+  } else {
+    const int r = rid - B * RN, k = r % RM;
+    tile0 = B * TN + (r / RM) * TM + k * S;
+    nt = min(S, TM - k * S);
+  }
+}
+
+// The run form of k_trunk4sp: a workgroup walks the run's tiles one after the other and carries the exact running maximum
+// (frun: 1024 floats per run in the workspace - the 160 KiB of LDS are taken and no LDS region survives a tile; no register
+// survives the 256-accumulator sweep).  Nothing passes between workgroups; the candidate sets are a function of the inputs
+// and S alone.
+struct TrunkRunArgs {
+  catre_points P;
+  const float *trans3, *trans64, *Wc1, *bc1;
+  const f32x4* wp2;
+  const float* b2;
+  const f32x4* wp3;
+  const float* b3;
+  const f32x4* wp4;
+  const float* b4;
+  float *pm, *pointfeat;
+  unsigned long long* trace;
+  ScreenArgs sc;
+  float* frun;  // [runs][1024]
+  int B, N, M, S;
+};
+
+__global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
+  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
+  // The arguments are read from the kernel-argument segment afresh in every tile (the pointer passes through an empty
+  // volatile asm, so the loads cannot leave the loop): held in scalar registers for the whole loop, the 64 dwords of
+  // arguments do not fit beside what the sweep needs, the excess goes to a vector register and the kernel spills.
+  // For the same reason the wave index stays in a scalar register and the lane id is computed afresh in every tile, so that
+  // neither threadIdx.x nor anything derived from a lane id is live across a tile's sweep (Trunk4ScreenT::store).
+  typedef const __attribute__((address_space(4))) TrunkRunArgs* ArgPtr;
+  ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)args;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int tile0, nt;
+  run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->S, tile0, nt);
+#pragma unroll 1
+  for (int t = 0; t < nt; ++t) {
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    asm volatile("" : "+s"(ap));
+    const TrunkRunArgs a = *(const TrunkRunArgs*)ap;  // (generic pointer for the copy; the loads stay scalar)
+    Trunk4ScreenT<true, true> tl;
+    tl.sc = a.sc;
+    tl.frun = a.frun + (size_t)blockIdx.x * 1024;
+    tl.first = t == 0;
+    trunk4_body<false>(smem, a.P, a.trans3, a.trans64, a.Wc1, a.bc1, a.wp2, a.b2, a.wp3, a.b3, a.wp4, a.b4, a.pm, a.pointfeat,
+                       a.B, a.N, a.M, a.trace, TrainSave{}, tl, tile0 + t, wave * 64 + lane);
+    __syncthreads();  // the next tile's prologue overwrites the a3 image the other waves still replay from
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -691,11 +809,14 @@ typedef ScreenPipe8<2, 8, false, LD128> StnScreenPipe;
 // scratch: LDS that is dead after conv2 (a1 / h1, 34 KiB): [0, 128) the row norms of both tiles, from float 128 on the
 // waves' candidate sets (4 x 4 KiB).  g holds the first sweep's first weight fragments (requested in front of conv2).
 // probe_rows (tests only): the image rows as [tile][64][128]
-template <int LAYER, bool POOL>
+// RUN: the run form (k_stn*_pair_sr) - frun = the 1024 running maxima of the run (LDS, -inf in front of the first tile;
+// first_pair: they are not to be read)
+template <int LAYER, bool POOL, bool RUN = false>
 __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnScreenPipe& g,
                                                    const f32x4* __restrict__ wp3, const float* __restrict__ b3,
                                                    float* __restrict__ pm, int tile0, int valid2, const ScreenArgs& sc,
-                                                   float* __restrict__ probe_rows, int wave, int tid, int lane) {
+                                                   float* __restrict__ probe_rows, int wave, int tid, int lane,
+                                                   float* frun = nullptr, bool first_pair = true) {
   const int nt = valid2 > TP ? 2 : 1, mb0 = wave * 8;
   screen_row_norms<128, 256, 2 * TP, false>(img, scratch, tid, LD128);
   if (probe_rows) {
@@ -716,8 +837,10 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
     // the lane id is computed afresh behind the sweep (see Trunk4Screen::store: the sweep leaves no register for it)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     const f32x4* wf = wp3 + ((size_t)mb0 * 16) * 64 + (ln & 31);
-    screen_select_store<8, 128, false, LAYER, POOL>(acc, wf, sc.nw, scratch + t * TP, x, sets, pm + (size_t)(tile0 + t) * PMW, b3,
-                                              mb0 * 32, true, min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128);
+    screen_select_store<8, 128, false, LAYER, POOL, RUN>(acc, wf, sc.nw, scratch + t * TP, x, sets,
+                                                         pm + (size_t)(tile0 + t) * PMW, b3, mb0 * 32, true,
+                                                         min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128, frun,
+                                                         first_pair && t == 0);
   };
   tile(0, lane);
   if (nt == 2) {  // (again a fresh lane id: nothing lane-dependent of the first tile stays live across its epilogue)
@@ -728,20 +851,23 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
 }
 
 // POOL: the pooled replay (screen_pool_store) - k_stn3d_pair_sp / k_stnkd_pair_sp
-template <bool POOL>
+// (bid, tid): blockIdx.x and threadIdx.x of the one-pair kernels; the run form walks several pairs (RUN, frun, first_pair)
+template <bool POOL, bool RUN = false>
 __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* __restrict__ W1,
                                                   const float* __restrict__ b1, const f32x4* __restrict__ wp2,
                                                   const float* __restrict__ b2, const f32x4* __restrict__ wp3,
                                                   const float* __restrict__ b3, float* __restrict__ pm, int B, int N,
-                                                  int M, const ScreenArgs& sc, float* __restrict__ probe_rows) {
+                                                  int M, const ScreenArgs& sc, float* __restrict__ probe_rows,
+                                                  const int bid, const int tid, float* frun = nullptr,
+                                                  bool first_pair = true) {
   __shared__ __attribute__((aligned(16))) float smem[2 * TP * LD64 + 2 * TP * LD128];
   float* a1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
   float* a2 = smem + 2 * TP * LD64;   // [128][132]
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   TileInfo ti;
   int tile0;
-  pair_info32(blockIdx.x, B, N, M, ti, tile0);
+  pair_info32(bid, B, N, M, ti, tile0);
 
   GemmPipe<1, 4, false, false, 8, 3> g2;  // conv2 64->128: wave -> m-block `wave`, all four point blocks
   g2.prefetch(wp2 + (wave * 8) * 64 + lane, 0);
@@ -762,7 +888,7 @@ __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, a2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<1, POOL>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
+  stn_conv3_screened<1, POOL, RUN>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
 #define STN3D_PAIR_S_(NAME, POOL)                                                                                          \
   __global__ __launch_bounds__(256) void NAME(catre_points P, const float* __restrict__ W1, const float* __restrict__ b1, \
@@ -770,29 +896,30 @@ __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* _
                                               const f32x4* __restrict__ wp3, const float* __restrict__ b3,                \
                                               float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,                 \
                                               float* __restrict__ probe_rows) {                                           \
-    stn3d_pair_s_body<POOL>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows);                                    \
+    stn3d_pair_s_body<POOL>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows, blockIdx.x, threadIdx.x);          \
   }
 STN3D_PAIR_S_(k_stn3d_pair_s, false)
 STN3D_PAIR_S_(k_stn3d_pair_sp, true)
 #undef STN3D_PAIR_S_
 
-template <bool POOL>
+template <bool POOL, bool RUN = false>
 __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* __restrict__ trans3,
                                                   const float* __restrict__ Wc1, const float* __restrict__ bc1,
                                                   const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
                                                   const f32x4* __restrict__ wpf2, const float* __restrict__ bf2,
                                                   const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,
                                                   float* __restrict__ pm, int B, int N, int M, const ScreenArgs& sc,
-                                                  float* __restrict__ probe_rows) {
+                                                  float* __restrict__ probe_rows, const int bid, const int tid,
+                                                  float* frun = nullptr, bool first_pair = true) {
   __shared__ __attribute__((aligned(16))) float smem[4 * TP * LD64 + 2 * TP * LD128];
   float* h1 = smem;                   // [128][68]; after conv2: row norms + candidate sets
   float* f1 = smem + 2 * TP * LD64;   // [128][68]
   float* f2 = smem + 4 * TP * LD64;   // [128][132]
-  const int tid = threadIdx.x, lane = tid & 63;
+  const int lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   TileInfo ti;
   int tile0;
-  pair_info32(blockIdx.x, B, N, M, ti, tile0);
+  pair_info32(bid, B, N, M, ti, tile0);
 
   const int mblk1 = wave >> 1, half1 = wave & 1;
   GemmPipe<1, 2, false, false, 8, 4> g1;  // fstn.conv1 64->64: wave -> (m-block, tile of the pair)
@@ -826,7 +953,7 @@ __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, f2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<2, POOL>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane);
+  stn_conv3_screened<2, POOL, RUN>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
 #define STNKD_PAIR_S_(NAME, POOL)                                                                                      \
   __global__ __launch_bounds__(256) void NAME(                                                                        \
@@ -834,8 +961,104 @@ __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* _
       const f32x4* __restrict__ wpf1, const float* __restrict__ bf1, const f32x4* __restrict__ wpf2,                  \
       const float* __restrict__ bf2, const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,                   \
       float* __restrict__ pm, int B, int N, int M, ScreenArgs sc, float* __restrict__ probe_rows) {                   \
-    stnkd_pair_s_body<POOL>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows);       \
+    stnkd_pair_s_body<POOL>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows,       \
+                            blockIdx.x, threadIdx.x);                                                                  \
   }
 STNKD_PAIR_S_(k_stnkd_pair_s, false)
 STNKD_PAIR_S_(k_stnkd_pair_sp, true)
 #undef STNKD_PAIR_S_
+
+// ------------------------------------------------------------------------------------------
+// Run forms of the pooled STN pair kernels (`screen_run`, its own arm CATRE_SCREEN_RUN_STN): a workgroup walks up to SP
+// consecutive PAIRS of one cloud - the loop is over pairs, the two tile copies inside stn_conv3_screened stay - and carries
+// the running maximum from tile to tile, the second tile of a pair included.  These kernels have LDS to spare: the 1024
+// running maxima live there.  Arguments, wave index and lane id are handled as in k_trunk4sr.
+// ------------------------------------------------------------------------------------------
+// run -> pairs, in pair_info32's numbering (observed clouds first; a cloud of P pairs has ceil(P / SP) runs)
+__device__ __forceinline__ void pair_run_info(int rid, int B, int N, int M, int SP, int& pair0, int& np) {
+  const int PN = ((N + TP - 1) / TP + 1) / 2, PM_ = ((M + TP - 1) / TP + 1) / 2;
+  const int RN = (PN + SP - 1) / SP, RM = (PM_ + SP - 1) / SP;
+  if (rid < B * RN) {
+    const int k = rid % RN;
+    pair0 = (rid / RN) * PN + k * SP;
+    np = min(SP, PN - k * SP);
+  } else {
+    const int r = rid - B * RN, k = r % RM;
+    pair0 = B * PN + (r / RM) * PM_ + k * SP;
+    np = min(SP, PM_ - k * SP);
+  }
+}
+
+struct Stn3dRunArgs {
+  catre_points P;
+  const float *W1, *b1;
+  const f32x4* wp2;
+  const float* b2;
+  const f32x4* wp3;
+  const float* b3;
+  float* pm;
+  const u32x4* wps;  // ScreenArgs without the probes: the probe calls keep the one-pair kernels
+  const float* nw;
+  int B, N, M, SP;
+};
+
+__global__ __launch_bounds__(256) void k_stn3d_pair_sr(Stn3dRunArgs args) {
+  __shared__ __attribute__((aligned(16))) float frun[1024];
+  typedef const __attribute__((address_space(4))) Stn3dRunArgs* ArgPtr;
+  ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)args;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int pair0, np;
+  pair_run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->SP, pair0, np);
+  // -inf in front of the first tile; every wave reads and writes its own 256 channels only
+  *reinterpret_cast<f32x4*>(frun + 4 * threadIdx.x) = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  __syncthreads();
+#pragma unroll 1
+  for (int bid = pair0, end = pair0 + np; bid < end; ++bid) {
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    asm volatile("" : "+s"(ap));
+    const Stn3dRunArgs a = *(const Stn3dRunArgs*)ap;
+    stn3d_pair_s_body<true, true>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
+                                  ScreenArgs{a.wps, a.nw, nullptr, nullptr}, nullptr, bid, wave * 64 + lane, frun, false);
+    __syncthreads();  // the next pair's conv1 overwrites the candidate sets, its conv2 the image the other waves replay from
+  }
+}
+
+struct StnkdRunArgs {
+  catre_points P;
+  const float *trans3, *Wc1, *bc1;
+  const f32x4* wpf1;
+  const float* bf1;
+  const f32x4* wpf2;
+  const float* bf2;
+  const f32x4* wpf3;
+  const float* bf3;
+  float* pm;
+  const u32x4* wps;  // ScreenArgs without the probes: the probe calls keep the one-pair kernels
+  const float* nw;
+  int B, N, M, SP;
+};
+
+__global__ __launch_bounds__(256) void k_stnkd_pair_sr(StnkdRunArgs args) {
+  __shared__ __attribute__((aligned(16))) float frun[1024];
+  typedef const __attribute__((address_space(4))) StnkdRunArgs* ArgPtr;
+  ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
+  (void)args;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int pair0, np;
+  pair_run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->SP, pair0, np);
+  // -inf in front of the first tile; every wave reads and writes its own 256 channels only
+  *reinterpret_cast<f32x4*>(frun + 4 * threadIdx.x) = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  __syncthreads();
+#pragma unroll 1
+  for (int bid = pair0, end = pair0 + np; bid < end; ++bid) {
+    int lane;
+    asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
+    asm volatile("" : "+s"(ap));
+    const StnkdRunArgs a = *(const StnkdRunArgs*)ap;
+    stnkd_pair_s_body<true, true>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N, a.M,
+                                  ScreenArgs{a.wps, a.nw, nullptr, nullptr}, nullptr, bid, wave * 64 + lane, frun, false);
+    __syncthreads();
+  }
+}

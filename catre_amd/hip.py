@@ -142,6 +142,8 @@ _SIGS = {
     "catre_refine_k": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
     "catre_stn_screen_probe": (_I, [_I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_form_switch": (_I, [_I, _I]),
+    "catre_screen_run_len": (_I, [_I]),
+    "catre_screen_run_rule": (_I, [_I, _I, _I, _I]),
     "catre_refine_k_from": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
     "catre_colmax": (_I, [_P, _P, _I, _I, _I, _P]),
     # training ops (include/catre_hip.h "training ops")
@@ -278,7 +280,8 @@ def bump_param_epoch():
     _param_epoch[0] += 1
 
 
-FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7}
+FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7,
+            "screen_run": 8}
 
 
 def form_switch(name, value=None):
@@ -288,6 +291,17 @@ def form_switch(name, value=None):
     if r < 0:
         raise CatreHipError(f"unknown kernel-form switch {name!r}")
     return bool(r)
+
+
+def screen_run_len(value=None):
+    """Run length of the `screen_run` form (tiles of one cloud a workgroup of k_trunk4sr walks): an int 1 .. 16 forces it,
+    0 returns to the library's rule (``screen_run_rule``), None only queries; returns the previous value (0: the rule)."""
+    return load().catre_screen_run_len(-1 if value is None else int(value))
+
+
+def screen_run_rule(B, N, M, cus=256):
+    """The run length the library's rule picks for a (B, N, M) grid on `cus` compute units (a pure host function)."""
+    return load().catre_screen_run_rule(B, N, M, cus)
 
 
 def capture_id(device):

@@ -313,14 +313,28 @@ int catre_profile_enable(int kernel_id, int max_records);
  * off turns every screened form off; the caveat about non-finite activations covers the STN layers too,
  * 7: the screened kernels replay their candidates from ONE list per wave (all 256 channels of the wave, rounds of 64
  * entries) instead of per-channel trips sized by the worst channel of a 32-channel block, k_trunk4sp - same bits as 5; it
- * refines 5 and has no effect while 5 is off; catre_trunk_screen_probe follows it),
+ * refines 5 and has no effect while 5 is off; catre_trunk_screen_probe follows it,
+ * 8: the pooled trunk as k_trunk4sr - a workgroup walks a RUN of up to S consecutive tiles of one cloud (S:
+ * catre_screen_run_len) and carries the exact running maximum, so that a tile replays only the points that can still beat
+ * it - same bits; likewise the pooled STN pair kernels as k_stn3d_pair_sr / k_stnkd_pair_sr on runs of S / 2 pairs (their
+ * own arm: CATRE_SCREEN_RUN_STN = 0, read once per process, leaves them on one pair); it refines 7 and so 5;
+ * catre_trunk_screen_probe follows it, catre_stn_screen_probe keeps the one-pair kernels),
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
- * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-7 on, 3 and 4 off -
+ * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-8 on, 3 and 4 off -
  * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
- * CATRE_SCREEN_STN / CATRE_SCREEN_POOL = 0,
+ * CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN = 0,
  * CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
  * launched with. */
 int catre_form_switch(int id, int value);
+/* Run length S of form 8 (tiles of one cloud a workgroup of k_trunk4sr walks).  value > 0 forces S = min(value, 16) for
+ * every later call (1: the one-tile kernel), 0 returns to the rule (catre_screen_run_rule with the device's CU count),
+ * value < 0 only queries.  Returns the previous value (0: the rule).  Process-wide, like the switches.  Any S gives the
+ * same bits. */
+int catre_screen_run_len(int value);
+/* The rule, a pure host function: the largest S in 2 .. 16 whose grid of B (ceil(TN / S) + ceil(TM / S)) workgroups,
+ * each up to S tiles long, takes no more tile slots on `cus` compute units (one workgroup per unit) than the one-tile
+ * grid - ceil(runs / cus) S <= ceil(tiles / cus) - else 1.  TN, TM: 64-point tiles of a cloud.  -1 for bad arguments. */
+int catre_screen_run_rule(int B, int N, int M, int cus);
 /* Experiment knobs of the instrumented library (id 0: start offset in cycles between the co-resident workgroups of the
  * STN kernels' first dispatch round, id 2: the screened kernels' counters of catre_debug_screen_counts on (1, default) / off
  * (0) - their atomics distort the phase stamps); CATRE_ERR_UNSUPPORTED in the product library. */

@@ -1,7 +1,9 @@
 """Candidate-count histograms and further-rounds shares of the three screened layers (kernel-form switches `screen` and
 `screen_stn`: trunk conv4, stn.conv3, fstn.conv3) on the bench inputs.  With `screen_pool` on (the default; CATRE_SCREEN_POOL=0
 for the per-channel replay) the kernels that replay from one list per wave report list entries and rounds of 64 per
-(wave, tile) instead of trips per 32-channel block.
+(wave, tile) instead of trips per 32-channel block.  With `screen_run` on (the default; CATRE_SCREEN_RUN=0 for one tile per
+workgroup, CATRE_SCREEN_RUN_STN=0 for the trunk alone) a workgroup carries the running maximum over a run of tiles: fewer
+entries, channels without a candidate (bin 0) and (wave, tile) units whose list is empty.
 
 Needs the instrumented library (`make -C catre_amd/csrc TRACE=1`), whose screened kernels count while they run:
     CATRE_HIP_LIB=catre_amd/csrc/libcatre_hip_trace.so python profiles/screen_candidates.py [out.txt]
@@ -35,13 +37,19 @@ model.refine(batch, n_iter=K)
 torch.cuda.synchronize()
 hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts")
 pool = hip.form_switch("screen_pool")
+run = pool and hip.form_switch("screen_run")
+run_stn = run and os.environ.get("CATRE_SCREEN_RUN_STN", "1") != "0"
+S = (hip.screen_run_len() or hip.screen_run_rule(B, N, M, torch.cuda.get_device_properties(0).multi_processor_count)) if run else 1
 lines = [f"B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights; screen_pool {'on' if pool else 'off'}; "
+         f"screen_run {'on, run length ' + str(S) + (' (STN kernels: ' + ('on' if run_stn else 'off') + ')') if run and S > 1 else 'off'}; "
          "per-channel replay: chains a lane carries at once: 4"]
 for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_s)", "fstn.conv3 (k_stnkd_pair_s)")):
     c = list(cnt)[64 * row:64 * row + 64]
     pooled = c[51] > 0   # only the pooled replay counts rounds
     if pooled:
         name = name.replace("_s)", "_sp)").replace("k_trunk4s", "k_trunk4sp")
+        if run and S > 1 and (row == 0 or run_stn):
+            name = name.replace("sp)", "sr)")
     lines.append(f"screened {name}")
     tot = sum(c[:32])
     mean = sum(i * v for i, v in enumerate(c[:32])) / max(tot, 1)
@@ -56,6 +64,7 @@ for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_
             if v:
                 lines.append(f"  {i:2d}: {v:10d}  {v / max(c[49], 1):.6f}")
         lines.append(f"(wave, tile) units whose list filled up (replayed in more than one batch): {c[48]} of {c[49]}")
+        lines.append(f"(wave, tile) units with an empty list: {c[52]} of {c[49]}")
         continue
     tt = sum(c[32:48])
     tmean = sum(i * v for i, v in enumerate(c[32:48])) / max(tt, 1)
