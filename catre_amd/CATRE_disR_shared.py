@@ -93,7 +93,7 @@ class CATRE_disR_shared(nn.Module):
             num_points = self.rot_head.num_points
             n = int(self.cfg.INPUT.get("NUM_PCL", num_points // 2))
             self._rt = HipRuntime(lambda: dict(self.named_parameters()), n, num_points - n, self._opts.ts_in_dim, root=self,
-                                  forms=self._head_forms())
+                                  forms=self._head_forms(), out_dim=int(getattr(self.pcl_net, "out_dim", 1024)))
         return self._rt
 
     def _head_forms(self):
@@ -317,6 +317,17 @@ def build_model_optimizer(cfg, is_test=False):
         params_lr_list.append(
             {"params": filter(lambda p: p.requires_grad, pcl_net.parameters()), "lr": float(cfg.SOLVER.BASE_LR)}
         )
+    # the heads' input widths follow the encoder's (the reference fails later, with a conv shape error at the first forward)
+    D = int(getattr(pcl_net, "out_dim", 1024))
+    th = cfg.MODEL.CATRE.TS_HEAD
+    rot_in, ts_in = int(cfg.MODEL.CATRE.ROT_HEAD.INIT_CFG.get("in_dim", 1024)), int(th.INIT_CFG.get("in_dim", 1024))
+    ts_want = ((D + 64) * (2 if th.WITH_KPS_FEATURE else 1) + 3 * int(bool(th.WITH_INIT_SCALE))
+               + 3 * int(bool(th.get("WITH_INIT_TRANS", False))))
+    if rot_in != D + 64:
+        raise ValueError(f"ROT_HEAD.INIT_CFG.in_dim={rot_in} does not match PCLNET.INIT_CFG.out_dim + 64 = {D + 64}")
+    if ts_in != ts_want:
+        raise ValueError(f"TS_HEAD.INIT_CFG.in_dim={ts_in} does not match the gathered feature width {ts_want} implied by "
+                         f"PCLNET.INIT_CFG.out_dim={D} and WITH_KPS_FEATURE / WITH_INIT_SCALE / WITH_INIT_TRANS")
     rot_head, rot_head_params = get_rot_head(cfg)
     params_lr_list.extend(rot_head_params)
     ts_head, ts_head_params = get_ts_head(cfg)
@@ -343,6 +354,7 @@ def expected_state_shapes(cfg):
     rd = int(net.ROT_HEAD.INIT_CFG.get("rot_dim", 3))
     ts_in = int(net.TS_HEAD.INIT_CFG.in_dim)
     ft = bool(net.PCLNET.INIT_CFG.get("feature_transform", False))
+    D = int(net.PCLNET.INIT_CFG.get("out_dim", 1024))
     s = {}
 
     def stn(prefix, k):
@@ -352,7 +364,7 @@ def expected_state_shapes(cfg):
             s[f"{prefix}.{name}.weight"], s[f"{prefix}.{name}.bias"] = (o, i), (o,)
 
     stn("pcl_net.stn", 3)
-    for name, o, i in (("conv1", 64, 3), ("conv2", 128, 64), ("conv3", 512, 128), ("conv4", 1024, 512)):
+    for name, o, i in (("conv1", 64, 3), ("conv2", 128, 64), ("conv3", 512, 128), ("conv4", D, 512)):
         s[f"pcl_net.{name}.weight"], s[f"pcl_net.{name}.bias"] = (o, i, 1), (o,)
     if ft:
         stn("pcl_net.fstn", 64)
@@ -371,7 +383,7 @@ def expected_state_shapes(cfg):
 
     for a in ("x", "y"):
         p = f"rot_head.rot_head_{a}"
-        F = head(p, net.ROT_HEAD.INIT_CFG, "layers", 1088, "GN")
+        F = head(p, net.ROT_HEAD.INIT_CFG, "layers", D + 64, "GN")
         s[f"{p}.neck.0.weight"], s[f"{p}.neck.0.bias"] = (rd, F, 1), (rd,)
         s[f"{p}.conv_p.weight"] = (1, P, 1)
         if net.ROT_HEAD.INIT_CFG.get("point_bias", True):

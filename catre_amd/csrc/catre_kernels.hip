@@ -989,6 +989,8 @@ __global__ __launch_bounds__(256) void k_trunk4(catre_points P, const float* __r
                     blockIdx.x, threadIdx.x);
 }
 
+#include "catre_trunkw.h"
+
 // ------------------------------------------------------------------------------------------
 // tile partial maxima -> per-cloud max:  out[cloud][c] = max_t pm[row(cloud,t)][c]
 // ------------------------------------------------------------------------------------------
@@ -2352,6 +2354,61 @@ int catre_trunk(const catre_points* pts, const float* trans3, const float* trans
   hipStream_t st = (hipStream_t)stream;
   launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st);
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
+  return check_launch();
+}
+
+// ---- the encoder at conv4 width out_dim (catre_trunkw.h) --------------------------------------------------------------
+// image: [the layout of catre_pack_weights for ts_in = 1 - the STN entry points read their packs at its offsets; its conv4
+// slots stay unwritten][conv4 as out_dim rows of fp32 fragments]
+static bool out_dim_ok(int d) { return d == 64 || d == 128 || d == 256 || d == 512 || d == 1024; }
+
+size_t catre_packed_floats_w(int out_dim) {
+  if (!out_dim_ok(out_dim)) return 0;
+  return pack_layout(1).total + (size_t)out_dim * 512;
+}
+
+int catre_pack_encoder_w(const float* const* prm, int out_dim, float* packed, size_t packed_floats, void* stream) {
+  REQUIRE(prm && packed);
+  if (!out_dim_ok(out_dim)) return CATRE_ERR_UNSUPPORTED;
+  REQUIRE(prm[CATRE_P_CONV4_W]);
+  const size_t base = pack_layout(1).total;
+  if (packed_floats < base + (size_t)out_dim * 512) return CATRE_ERR_WORKSPACE;
+  const float* enc[CATRE_P_COUNT];
+  for (int i = 0; i < CATRE_P_COUNT; ++i) enc[i] = prm[i];
+  enc[CATRE_P_CONV4_W] = nullptr;  // skipped there: catre_pack_weights_sel reads conv4 as [1024,512]
+  const int s = catre_pack_weights_sel(enc, 1, 1, 1, packed, packed_floats, CATRE_PACK_F32_ENCODER, stream);
+  if (s != CATRE_OK) return s;
+  const int n = out_dim * 512;
+  hipLaunchKernelGGL(k_pack_frag, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, prm[CATRE_P_CONV4_W], 512, 0,
+                     out_dim, 512, packed + base);
+  return check_launch();
+}
+
+int catre_trunk_w(const catre_points* pts, const float* trans3, const float* trans64, const float* const* prm,
+                  const float* packed, int out_dim, float* gfeat, float* pointfeat, void* workspace, size_t ws_bytes, int B,
+                  int N, int M, void* stream) {
+  REQUIRE(pts && trans3 && prm && packed && gfeat && pointfeat && workspace && dims_ok1(B, N, M));
+  if (!out_dim_ok(out_dim)) return CATRE_ERR_UNSUPPORTED;
+  const WsLayout W = ws_layout(B, N, M);
+  if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
+  float* ws = (float*)workspace;
+  hipStream_t st = (hipStream_t)stream;
+  const PackLayout L = pack_layout(1);
+  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
+#define LAUNCH_(MB, NB)                                                                                                \
+  hipLaunchKernelGGL((k_trunkw<MB, NB>), dim3(tiles), dim3(512), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],   \
+                     prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),                 \
+                     prm[CATRE_P_CONV3_B], pk4(packed, L.total), prm[CATRE_P_CONV4_B], out_dim / 32, ws + W.pm,        \
+                     pointfeat, B, N, M)
+  switch (out_dim) {
+    case 1024: LAUNCH_(4, 2); break;
+    case 512: LAUNCH_(2, 2); break;
+    case 256: LAUNCH_(1, 2); break;
+    default: LAUNCH_(1, 1);  // 128, 64
+  }
+#undef LAUNCH_
+  hipLaunchKernelGGL(k_reduce_pm_w, dim3(n_clouds(B, M), (out_dim + 64 + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat,
+                     out_dim, B, N, M);
   return check_launch();
 }
 

@@ -36,6 +36,11 @@ _INPUTS = ("x", "tfd_kps", "init_pose", "init_scale", "K_zoom", "gt_ego_rot", "g
 
 def _require_shipped_heads(model, what):
     """The captured chains are the fused ones: heads of another form run a host-side layer loop that is not captured."""
+    out_dim = int(getattr(getattr(model, "pcl_net", None), "out_dim", 1024))
+    if out_dim != 1024:
+        raise NotImplementedError(f"{what} captures the fused kernels, which are built for PCLNET.INIT_CFG.out_dim=1024; with "
+                                  f"out_dim={out_dim} call model.refine / model.forward directly (fp32, bf16 / autocast or "
+                                  "split)")
     forms = getattr(model, "_head_forms", None)
     if forms is not None:
         from .heads import SHIPPED_FORM

@@ -113,9 +113,9 @@ class RotHead(nn.Module):
         super().__init__()
         if kernel_size != 1:
             raise NotImplementedError(f"HIP rot head: kernel_size={kernel_size} is not built (the heads are 1x1 convolutions)")
-        if in_dim != 1088:
-            raise NotImplementedError(f"HIP rot head: in_dim={in_dim} is not built - its input is cat(1024 pooled, 64 "
-                                      "point-feature) channels: in_dim=1088")
+        if in_dim not in [d + 64 for d in hip.OUT_DIMS]:
+            raise NotImplementedError(f"HIP rot head: in_dim={in_dim} is not built - its input is cat(out_dim pooled, 64 "
+                                      f"point-feature) channels: in_dim = out_dim + 64 for out_dim in {set(hip.OUT_DIMS)}")
         if not 1 <= int(rot_dim) <= 3:
             raise NotImplementedError(f"HIP rot head: rot_dim={rot_dim} is not built - rot_dim in {{1,2,3}} (3: rot6d, "
                                       "2: quat)")
@@ -143,7 +143,7 @@ class RotHead(nn.Module):
                 nn.init.constant_(m.bias, 0.0)
 
     def forward(self, x):
-        """x [B,1088,P] -> (r [B,rot_dim], feat [B,rot_dim,P]) like the reference (``:126-140``): per layer conv -> norm ->
+        """x [B,in_dim,P] -> (r [B,rot_dim], feat [B,rot_dim,P]) like the reference (``:126-140``): per layer conv -> norm ->
         act, then neck = feat -> conv_p over the points."""
         from . import train_ops as T
 

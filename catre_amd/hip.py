@@ -64,6 +64,7 @@ PACK_F16 = 32       # CATRE_PACK_F16: the fp16 packs DTYPE_F16 reads (not part o
 ROT_6D, ROT_QUAT, ROT_LOG_QUAT, ROT_LIE_VEC = 0, 1, 2, 3
 ACT_NONE, ACT_RELU, ACT_LRELU, ACT_SILU, ACT_GELU, ACT_MISH = range(6)   # CATRE_ACT_*
 ROT_DIMS = {ROT_6D: 6, ROT_QUAT: 4, ROT_LOG_QUAT: 3, ROT_LIE_VEC: 3}
+OUT_DIMS = (64, 128, 256, 512, 1024)   # PCLNET.INIT_CFG.out_dim (conv4's width) the kernels are built for; 1024: every shipped config
 
 
 def rot_type_id(rot_type):
@@ -131,6 +132,9 @@ _SIGS = {
     "catre_linear_t": (_I, [_P, _I, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "catre_stnkd_pool": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_trunk": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
+    "catre_packed_floats_w": (_SZ, [_I]),
+    "catre_pack_encoder_w": (_I, [_P, _I, _P, _SZ, _P]),
+    "catre_trunk_w": (_I, [_P, _P, _P, _P, _P, _I, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_trunk_screen_probe": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),
     "catre_ts_head": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _P]),
     "catre_rot_head": (_I, [_P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _P]),

@@ -93,8 +93,9 @@ class PointNetfeat(nn.Module):
 
     def __init__(self, num_points, global_feat=True, out_dim=1024, feature_transform=False, **args):
         super().__init__()
-        if out_dim != 1024:
-            raise NotImplementedError("the HIP trunk is built for out_dim=1024 (every shipped config)")
+        if out_dim not in hip.OUT_DIMS:
+            raise NotImplementedError(f"out_dim={out_dim!r}: the HIP trunk is built for out_dim in {set(hip.OUT_DIMS)} "
+                                      "(conv4 = Conv1d(512, out_dim))")
         self.num_points = num_points
         self.out_dim = out_dim
         self.feature_transform = feature_transform
@@ -115,24 +116,28 @@ class PointNetfeat(nn.Module):
 
     def _runtime(self):
         if self._rt is None:
-            self._rt = HipRuntime(lambda: {f"pcl_net.{k}": v for k, v in self.named_parameters()}, 1, 1, 1)
+            self._rt = HipRuntime(lambda: {f"pcl_net.{k}": v for k, v in self.named_parameters()}, 1, 1, 1,
+                                  out_dim=self.out_dim)
         return self._rt
 
     def forward(self, x, **args):
-        """x [B,3,n] -> [B,1024] (global_feat) or [B,1088,n] = cat(global repeated, pointfeat)."""
+        """x [B,3,n] -> [B,out_dim] (global_feat) or [B,out_dim+64,n] = cat(global repeated, pointfeat)."""
         n_pts = x.shape[2]
         if _needs_grad(self, x):
             from .train_forward import _points_rows, pointnet_rows
+            from .train_ops import amp_mode
 
             hip.require_dev_f32(x, "x", (x.shape[0], 3, n_pts), contiguous=False)
-            g, pf = pointnet_rows(_points_rows(x), {f"m.{k}": v for k, v in self.named_parameters()}, x.shape[0], n_pts, 0,
-                                  self.feature_transform, prefix="m")
+            # out_dim != 1024: fp32 in every compute mode, like the no-grad route (catre_trunk_w is an fp32 kernel)
+            with amp_mode("fp32" if self.out_dim != 1024 else None):
+                g, pf = pointnet_rows(_points_rows(x), {f"m.{k}": v for k, v in self.named_parameters()}, x.shape[0], n_pts,
+                                      0, self.feature_transform, prefix="m")
             st = {"gfeat": g, "pointfeat": pf}
         else:
             st = self._runtime().stage_pointnet(x, None, self.feature_transform)
         g = st["gfeat"][:, : self.out_dim]
         if self.global_feat:
             return g.contiguous()
-        # materialising the as-written [B,1088,n] tensor is plain data movement (pointnet.py:120-121)
+        # materialising the as-written [B,out_dim+64,n] tensor is plain data movement (pointnet.py:120-121)
         pointfeat = st["pointfeat"].view(x.shape[0], n_pts, 64).permute(0, 2, 1)
         return torch.cat([g.unsqueeze(-1).expand(-1, -1, n_pts), pointfeat], 1)

@@ -45,7 +45,8 @@ def opts_from_cfg(cfg, feature_transform=True):
     o.zero_center = int(bool(cfg.INPUT.ZERO_CENTER_INPUT))
     o.delta_t_weight = float(rh.DELTA_T_WEIGHT)
     o.allo_eps = 1e-4  # CATRE_disR_shared.py:112
-    o.ts_in_dim = 1088 * (2 if o.with_kps_feature else 1) + 3 * o.with_init_scale + 3 * o.with_init_trans
+    gw = int(net.PCLNET.INIT_CFG.get("out_dim", 1024)) + 64   # gathered feature of one cloud: [max_n conv4 | max_n pointfeat]
+    o.ts_in_dim = gw * (2 if o.with_kps_feature else 1) + 3 * o.with_init_scale + 3 * o.with_init_trans
     o.rot_type = rot_type
     return o
 
@@ -59,20 +60,26 @@ class HipRuntime:
     the image is only read); a training stream next to a concurrent inference stream - or a ``GraphedRefine`` replay -
     on the SAME runtime is not supported: use a second model instance (``copy.deepcopy`` drops the runtime)."""
 
-    def __init__(self, named_params, N, M, ts_in_dim, root=None, forms=None):
+    def __init__(self, named_params, N, M, ts_in_dim, root=None, forms=None, out_dim=1024):
         """``named_params``: callable returning ``{state_dict key: tensor}`` of the LIVE parameters.  ``forms`` (optional):
         (rot head, ts head) ``heads.HeadForm``; with a head that is not the shipped form the fused head kernels and their
         weight packs are not used (`layered`).  ``root`` (optional):
         the module whose ``named_parameters()`` keys are the state_dict keys as they are - lets ``_live_params`` read the
         parameters through cached ``module._parameters`` slots instead of walking the module tree on every call (the walk
-        was 60 % of a forward's host time at B=1, profiles/eval_loop_cprofile.py)."""
+        was 60 % of a forward's host time at B=1, profiles/eval_loop_cprofile.py).  ``out_dim``: conv4's width
+        (``PCLNET.INIT_CFG.out_dim``); anything but 1024 is `layered` as well, and its encoder image and trunk are
+        ``catre_pack_encoder_w`` / ``catre_trunk_w`` - every other entry point that takes ``params`` reads conv4 as
+        [1024,512] and rot layer 0 as [256,1088] and is never handed this model's weights (``_require_1024``)."""
         self._named_params = named_params
         self._root = root
         from .heads import SHIPPED_FORM
 
         self.forms = tuple(forms) if forms is not None else (SHIPPED_FORM, SHIPPED_FORM)
         # a head of another form: the heads run layer by layer (train_forward.heads_rows), and the packs hold the encoder only
-        self.layered = any(f != SHIPPED_FORM for f in self.forms)
+        self.out_dim = int(out_dim)
+        if self.out_dim not in hip.OUT_DIMS:
+            raise NotImplementedError(f"out_dim={out_dim!r}: built for out_dim in {set(hip.OUT_DIMS)}")
+        self.layered = any(f != SHIPPED_FORM for f in self.forms) or self.out_dim != 1024
         self._slots = None
         self._links = None
         self.N, self.M, self.ts_in_dim = int(N), int(M), int(ts_in_dim)
@@ -114,6 +121,9 @@ class HipRuntime:
         caller needs (``hip.PACK_*``); a training step, which re-packs after every optimizer step, asks for the fp32
         encoder image only."""
         lib = hip.load()
+        wide = self.out_dim != 1024   # the image is catre_pack_encoder_w's whatever `sel` asks for: there are no other packs
+        if wide:
+            sel = hip.PACK_F32_ENCODER
         tensors = self._live_params()
         fp = (hip.param_epoch(),) + tuple((t.data_ptr(), t._version) if t is not None else None for t in tensors)
         capturing = torch.cuda.is_current_stream_capturing()
@@ -138,14 +148,20 @@ class HipRuntime:
             tensors = [t.detach().contiguous() if t is not None else None for t in tensors]
             self._param_keep = tensors
             self._param_arr = hip.param_array(tensors)
-            n = lib.catre_packed_floats(self.N, self.M, self.ts_in_dim)
+            n = lib.catre_packed_floats_w(self.out_dim) if wide else lib.catre_packed_floats(self.N, self.M, self.ts_in_dim)
             if self._packed is None or self._packed.numel() < n or self._packed.device != device:
                 self._packed = torch.empty(n, dtype=torch.float32, device=device)
-            hip.check(
-                lib.catre_pack_weights_sel(self._param_arr, self.N, self.M, self.ts_in_dim, hip.ptr(self._packed),
-                                           self._packed.numel(), int(sel), hip.stream_ptr(device)),
-                "catre_pack_weights_sel",
-            )
+            if wide:
+                if tuple(self._param_keep[hip.PARAM_KEYS.index("pcl_net.conv4.weight")].shape[:2]) != (self.out_dim, 512):
+                    raise hip.CatreHipError(f"pcl_net.conv4.weight is not [{self.out_dim},512,1]")
+                hip.check(lib.catre_pack_encoder_w(self._param_arr, self.out_dim, hip.ptr(self._packed), self._packed.numel(),
+                                                   hip.stream_ptr(device)), "catre_pack_encoder_w")
+            else:
+                hip.check(
+                    lib.catre_pack_weights_sel(self._param_arr, self.N, self.M, self.ts_in_dim, hip.ptr(self._packed),
+                                               self._packed.numel(), int(sel), hip.stream_ptr(device)),
+                    "catre_pack_weights_sel",
+                )
             # a pack issued while the stream is being captured is only RECORDED (GraphedTrainStep): the buffer still holds
             # whatever the last executed pack wrote, so the cache must not call it fresh
             self._fingerprint = None if capturing else fp
@@ -153,6 +169,11 @@ class HipRuntime:
             if capturing:
                 self._capture_fp = (cap_key, int(sel))
         return self._param_arr, self._packed
+
+    def _require_1024(self, what):
+        if self.out_dim != 1024:
+            raise NotImplementedError(f"{what} is built for PCLNET.INIT_CFG.out_dim=1024; out_dim={self.out_dim} runs its "
+                                      "encoder on catre_trunk_w and its heads layer by layer")
 
     # ------------------------------------------------------------------ workspace
     def workspace(self, B, N, M, device):
@@ -265,13 +286,16 @@ class HipRuntime:
 
         mode = self._LAYERED_MODES.get(int(opts.compute_dtype))
         if mode is None:
+            if self.out_dim != 1024:
+                raise NotImplementedError(f"MODEL.CATRE.COMPUTE_DTYPE='fp16' is built for PCLNET.INIT_CFG.out_dim=1024; "
+                                          f"out_dim={self.out_dim} runs in 'fp32', 'bf16' (or torch.autocast) and 'split'")
             raise NotImplementedError("MODEL.CATRE.COMPUTE_DTYPE='fp16' is built for the shipped head form (feat_dim=256, "
                                       "num_layers=2, GN with 32 groups, gelu); heads of another form run in 'fp32', 'bf16' "
                                       "(or torch.autocast) and 'split'")
         B, N, M = x.shape[0], x.shape[2], tfd_kps.shape[2]
         with torch.no_grad(), T.amp_mode(mode):
             st = self.stage_pointnet(x, tfd_kps, feature_transform=bool(opts.feature_transform))
-            g, pfmax = st["gfeat"][:, :1024], st["gfeat"][:, 1024:]
+            g, pfmax = st["gfeat"][:, :self.out_dim], st["gfeat"][:, self.out_dim:]
             pf_obj = T.object_major(st["pointfeat"], B, N, M)
             p = {k: v.detach() for k, v in self._named_params().items()}
             rot, dt, ds = TF.heads_rows(p, opts, self.forms, g, pfmax, pf_obj, init_pose, init_scale, B, N, M,
@@ -306,6 +330,7 @@ class HipRuntime:
         """(params, packed) for the fused training forward in `mode` (0 = fp32 kernels: encoder AND head images, the rotation
         heads' fused forward reads the latter; 1 = bf16-operand kernels; 2 = split: its trunk keeps conv2 as an fp32 MFMA
         layer, so it reads the fp32 encoder image as well)."""
+        self._require_1024("the fused training forward")
         return self.params(device, {0: hip.PACK_F32_ENCODER | hip.PACK_F32_HEADS, 1: hip.PACK_BF16,
                                     2: hip.PACK_SPLIT | hip.PACK_F32_ENCODER}[int(mode)])
 
@@ -361,7 +386,7 @@ class HipRuntime:
     def stage_pointnet(self, x, tfd_kps=None, feature_transform=True):
         """PointNetfeat stages on x [B,3,N] (and optionally tfd_kps [B,3,M]) -> dict with
         ``trans [C,3,3]``, ``trans_feat [C,64,64]``, ``stn_pool``/``fstn_pool [C,1024]``,
-        ``gfeat [C,1088]``, ``pointfeat`` (flat [B*(N+M),64], observed clouds first); C = B or 2B."""
+        ``gfeat [C,out_dim+64]``, ``pointfeat`` (flat [B*(N+M),64], observed clouds first); C = B or 2B."""
         lib = hip.load()
         dev = x.device
         B, N = x.shape[0], x.shape[2]
@@ -392,10 +417,15 @@ class HipRuntime:
             out["fstn_pool"] = pool2
             t64 = self._stn_tail(pool2, named, "pcl_net.fstn", 64)
             out["trans_feat"] = t64.view(C, 64, 64)
-        gfeat = torch.empty(C, 1088, dtype=torch.float32, device=dev)
+        gfeat = torch.empty(C, self.out_dim + 64, dtype=torch.float32, device=dev)
         pointfeat = torch.empty(B * (N + M), 64, dtype=torch.float32, device=dev)
-        hip.check(lib.catre_trunk(ctypes.byref(pts), hip.ptr(trans), hip.ptr(t64), prm, hip.ptr(packed), hip.ptr(gfeat),
-                                  hip.ptr(pointfeat), hip.ptr(ws), ws.numel(), B, N, M, st), "catre_trunk")
+        if self.out_dim != 1024:
+            hip.check(lib.catre_trunk_w(ctypes.byref(pts), hip.ptr(trans), hip.ptr(t64), prm, hip.ptr(packed), self.out_dim,
+                                        hip.ptr(gfeat), hip.ptr(pointfeat), hip.ptr(ws), ws.numel(), B, N, M, st),
+                      "catre_trunk_w")
+        else:
+            hip.check(lib.catre_trunk(ctypes.byref(pts), hip.ptr(trans), hip.ptr(t64), prm, hip.ptr(packed), hip.ptr(gfeat),
+                                      hip.ptr(pointfeat), hip.ptr(ws), ws.numel(), B, N, M, st), "catre_trunk")
         out["gfeat"], out["pointfeat"] = gfeat, pointfeat
         return out
 
@@ -403,6 +433,7 @@ class HipRuntime:
         lib = hip.load()
         dev = gfeat.device
         B = init_scale.shape[0]
+        self._require_1024("catre_ts_head")
         prm, packed = self.params(dev)
         dt = torch.empty(B, 3, dtype=torch.float32, device=dev)
         ds = torch.empty(B, 3, dtype=torch.float32, device=dev)
@@ -416,6 +447,7 @@ class HipRuntime:
     def stage_rot_head(self, gfeat, pointfeat, B, N, M, rot_dim=3):
         lib = hip.load()
         dev = gfeat.device
+        self._require_1024("catre_rot_head_dim")
         prm, packed = self.params(dev)
         ws = self.workspace(B, N, M, dev)
         rot6d = torch.empty(B, 2 * rot_dim, dtype=torch.float32, device=dev)

@@ -97,7 +97,7 @@ def fused_lp_ok(pts, p, N, M, prefix="pcl_net"):
 
 
 def pointnet_rows(pts, p, B, N, M, feature_transform=True, prefix="pcl_net"):
-    """PointNetfeat on cloud-major point rows [B*N + B*M, 3] -> (g [C,1024], pointfeat [R,64])  (pointnet.py:97-116)."""
+    """PointNetfeat on cloud-major point rows [B*N + B*M, 3] -> (g [C,out_dim], pointfeat [R,64])  (pointnet.py:97-116)."""
     w = lambda n: p[f"{prefix}.{n}"]
     trans = _stn(pts, p, f"{prefix}.stn", 3, B, N, M)
     x1 = T.cloud_matmul(pts, trans, B, N, M, out_cols=8)                    # x^T @ trans, zero-padded to 8 columns
@@ -113,12 +113,19 @@ def pointnet_rows(pts, p, B, N, M, feature_transform=True, prefix="pcl_net"):
     return g, pf
 
 
+def _split_w0(W0):
+    """Rot-head layer 0's weight [F, D + 64(, 1)] -> (global half [F, D] (a view), point half [F, 64]): D, the encoder's
+    out_dim, is read from the weight."""
+    F, K = W0.shape[:2]
+    return T.split_cols(W0.reshape(F, K), K - 64)
+
+
 def _rot_head(g, pf_obj, p, prefix, B, N, M, x_cm=False):
     """RotHead.forward (heads/conv_out_per_rot_head.py:126-140) on the never-materialised cat(pcl_feat,kps_feat).  x_cm: pf_obj
     is pointfeat in CLOUD-major row order (only the autocast one-node head takes that: forward_train decided so)."""
     w = lambda n: p[f"{prefix}.{n}"]
     P = N + M
-    W0g, W0b = T.split_cols(w("layers.0.weight").reshape(256, 1088), 1024)   # global half (a view) | point half
+    W0g, W0b = _split_w0(w("layers.0.weight"))                                # global half (a view) | point half
     bias0 = T.linear(g, W0g, w("layers.0.bias"))                              # [2B,256]: global half + conv bias
     if T.rot_head_lp_ok(pf_obj, W0b, w("layers.3.weight"), w("layers.3.bias"), N, M):
         # autocast: the head as one node with bf16 [B*P,256] activations between its kernels
@@ -163,8 +170,8 @@ def _rot_head(g, pf_obj, p, prefix, B, N, M, x_cm=False):
 
 def _rot_head_form(g, pf_obj, p, prefix, B, N, M, form, fused_tail=False):
     """RotHead.forward for a head of any configured form (``heads.HeadForm``: width, depth, GroupNorm on / off and groups,
-    activation).  Layer 0 keeps the restructuring of the shipped route at any width: the global half ``W0[:, :1024] g`` is a
-    per-cloud bias, the point half runs on pointfeat - the ``[B,1088,P]`` tensor is never built.  The matrix work is
+    activation).  Layer 0 keeps the restructuring of the shipped route at any width: the global half ``W0[:, :D] g`` is a
+    per-cloud bias, the point half runs on pointfeat - the ``[B,D+64,P]`` tensor is never built.  The matrix work is
     ``T.linear`` / ``T.linear_cloudbias`` (tiled MFMA kernel at widths 32..256 in steps of 32, 512 and 1024; the small
     GEMM - correct, slow - elsewhere), norm + activation the generic ops.  fused_tail (nothing needs a gradient): the last
     layer's norm + act, neck and conv_p are one op."""
@@ -173,7 +180,7 @@ def _rot_head_form(g, pf_obj, p, prefix, B, N, M, form, fused_tail=False):
     w = lambda n: p[f"{prefix}.{n}"]
     P, F, L = N + M, form.feat_dim, form.num_layers
     gn = lambda i: (w(f"layers.{3 * i + 1}.weight"), w(f"layers.{3 * i + 1}.bias")) if form.norm else (None, None)
-    W0g, W0b = T.split_cols(w("layers.0.weight").reshape(F, 1088), 1024)     # global half (a view) | point half
+    W0g, W0b = _split_w0(w("layers.0.weight"))                                # global half (a view) | point half
     bias0 = T.linear(g, W0g, w("layers.0.bias"))                              # [2B,F]: global half + conv bias
     y = T.linear_cloudbias(pf_obj, W0b, bias0, B, N, M)
     rd = w("neck.0.weight").shape[0]
@@ -206,7 +213,7 @@ def _ts_head(ts_feat, p, form):
 
 
 def heads_rows(p, opts, forms, g, pfmax, pf_obj, init_pose, init_scale, B, N, M, fused_tail=False):
-    """Both heads layer by layer from the encoder's outputs (g [2B,1024] pooled, pfmax [2B,64] max_n pointfeat, pf_obj
+    """Both heads layer by layer from the encoder's outputs (g [2B,out_dim] pooled, pfmax [2B,64] max_n pointfeat, pf_obj
     [B*(N+M),64] object-major) -> (rot [B, 2 rot_dim], dt, ds): the route of heads that are not the shipped form - training,
     and with fused_tail the no-grad forward / refine."""
     rot_form, ts_form = forms
@@ -238,7 +245,7 @@ def _rot_heads_lp(g, pf, p, B, N, M, x_cm):
     heads = []
     for h, pre in enumerate(_ROT_PREFIX):
         w = lambda n: p[f"{pre}.{n}"]
-        W0g, W0b = T.split_cols(w("layers.0.weight").reshape(256, 1088), 1024)
+        W0g, W0b = _split_w0(w("layers.0.weight"))
         bias0 = T.linear(g[h], W0g, w("layers.0.bias"))
         wn, bn = neck_weight3(w("neck.0.weight"), w("neck.0.bias"))
         heads.append((W0b, bias0, w("layers.1.weight"), w("layers.1.bias"), w("layers.3.weight"), w("layers.3.bias"),
@@ -251,14 +258,14 @@ def _rot_heads_shapes_ok_p(p, N, M):
     """:func:`_rot_heads_shapes_ok` before pointfeat exists (its width is pcl_net.conv1's: 64)."""
     return (tuple(p["pcl_net.conv1.weight"].shape[:1]) == (64,) and N % 64 == 0 and M % 64 == 0 and N > 0 and M > 0
             and all(p.get(f"{pre}.layers.3.bias") is not None
-                    and tuple(p[f"{pre}.layers.0.weight"].shape[:2]) == (256, 1088)
+                    and tuple(p[f"{pre}.layers.0.weight"].shape[:2]) == (256, p["pcl_net.conv4.weight"].shape[0] + 64)
                     and tuple(p[f"{pre}.layers.3.weight"].shape[:2]) == (256, 256) for pre in _ROT_PREFIX))
 
 
 def _rot_heads_shapes_ok(p, pf_obj, N, M):
     return (pf_obj.shape[1] == 64 and N % 64 == 0 and M % 64 == 0 and N > 0 and M > 0
             and all(p.get(f"{pre}.layers.3.bias") is not None
-                    and tuple(p[f"{pre}.layers.0.weight"].shape[:2]) == (256, 1088)
+                    and tuple(p[f"{pre}.layers.0.weight"].shape[:2]) == (256, p["pcl_net.conv4.weight"].shape[0] + 64)
                     and tuple(p[f"{pre}.layers.3.weight"].shape[:2]) == (256, 256) for pre in _ROT_PREFIX))
 
 
@@ -276,7 +283,7 @@ def _rot_heads_split(g, pf, pf_obj, p, rt, B, N, M):
     P = N + M
     W0s, b0s = [], []
     for h, pre in enumerate(_ROT_PREFIX):
-        W0g, W0l = T.split_cols(p[f"{pre}.layers.0.weight"].reshape(256, 1088), 1024)
+        W0g, W0l = _split_w0(p[f"{pre}.layers.0.weight"])
         W0s.append(W0l)
         b0s.append(T.linear(g[h], W0g, p[f"{pre}.layers.0.bias"]))   # [2B,256]
     prm, packed = rt._train_packs(pf.device, 2)
@@ -318,7 +325,7 @@ def _rot_heads_fused(g, pf, pf_obj, p, rt, B, N, M):
     heads = []
     for h, pre in enumerate(_ROT_PREFIX):
         w = lambda n: p[f"{pre}.{n}"]
-        W0g, W0l = T.split_cols(w("layers.0.weight").reshape(256, 1088), 1024)   # global half | point half
+        W0g, W0l = _split_w0(w("layers.0.weight"))                               # global half | point half
         bias0 = T.linear(g[h], W0g, w("layers.0.bias"))                           # [2B,256]: global half + conv bias
         wn, bn = neck_weight3(w("neck.0.weight"), w("neck.0.bias"))
         heads.append((bias0, W0l, w("layers.1.weight"), w("layers.1.bias"), w("layers.3.weight"),
@@ -342,6 +349,7 @@ def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_
     # the packed head image, are not taken then - the per-head ops are)
     rot_packed = rot_shipped and not getattr(rt, "layered", False)
     B, N, M = x.shape[0], x.shape[2], tfd_kps.shape[2]
+    D = p["pcl_net.conv4.weight"].shape[0]   # PCLNET.INIT_CFG.out_dim; the fused encoder / head forwards are built for 1024
     hip.require_dev_f32(x, "x", (B, 3, N), contiguous=False)
     hip.require_dev_f32(tfd_kps, "tfd_kps", (B, 3, M), contiguous=False)
     # one decision, taken once: the fused fp32 rotation heads read pointfeat cloud-major (forward AND backward), so no
@@ -349,21 +357,25 @@ def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_
     fused_rot = (rot_packed and rt is not None and T._amp() == 0 and bool(opts.feature_transform)
                  and N + M == rt.N + rt.M and _rot_heads_shapes_ok_p(p, N, M))
     # autocast: each head is one node (train_ops._RotHeadLP) that reads pointfeat cloud-major as well - no object-major copy
-    lp_cm = (rot_shipped and rt is not None and T._amp() == 1 and T.knobs().fused_lp_rot and T.knobs().lp_rot_bf16_rows
+    lp_cm = (rot_shipped and D == 1024 and rt is not None and T._amp() == 1 and T.knobs().fused_lp_rot and T.knobs().lp_rot_bf16_rows
              and bool(opts.feature_transform) and N + M == rt.N + rt.M and _rot_heads_shapes_ok_p(p, N, M))
+    # D != 1024: the encoder is fp32 in every compute mode, with and without grad - its no-grad trunk (catre_trunk_w) is an
+    # fp32 kernel, and a model's training forward and its no-grad forward take the same encoder precision; the heads follow
+    # the mode
+    enc_fp32 = D != 1024
     enc_frozen = (not x.requires_grad and not tfd_kps.requires_grad
                   and not any(v.requires_grad for k, v in p.items() if k.startswith("pcl_net.")))
-    if rt is not None and enc_frozen and T._amp() == 0 and N + M == rt.N + rt.M:
+    if rt is not None and enc_frozen and (T._amp() == 0 or enc_fp32) and N + M == rt.N + rt.M:
         # PCLNET.FREEZE (CATRE_disR_shared.py:301-304): nothing in front of the heads needs a gradient, so the encoder runs
         # on the INFERENCE kernels - no activation saves, no arg-max rows, no graph nodes (and no encoder backward)
         # like train_stn3d: the first kernel of a training forward re-packs what it reads - the fingerprint cannot see writes
         # through `p.data` (the reference's own Ranger, EMA), and the heads' backward reads the LIVE w0 / w1
         rt._fingerprint = None
         st = rt.stage_pointnet(x, tfd_kps, feature_transform=bool(opts.feature_transform))
-        g, pfmax, pf = st["gfeat"][:, :1024], st["gfeat"][:, 1024:], st["pointfeat"]
+        g, pfmax, pf = st["gfeat"][:, :D], st["gfeat"][:, D:], st["pointfeat"]
         hub = (pfmax, pf if fused_rot else T.object_major(pf, B, N, M))
-    elif rt is not None and T._amp() in (0, 1, 2) and opts.feature_transform and N % 64 == 0 and M % 64 == 0 \
-            and N + M == rt.N + rt.M:
+    elif rt is not None and D == 1024 and T._amp() in (0, 1, 2) and opts.feature_transform and N % 64 == 0 \
+            and M % 64 == 0 and N + M == rt.N + rt.M:
         pts = _cloud_major_rows(x, tfd_kps)
         if T._amp() == 1 and not fused_lp_ok(pts, p, N, M):
             (g, pf), hub = pointnet_rows(pts, p, B, N, M, True), None   # (e.g. a differentiable 3-d input: layer-wise ops)
@@ -374,13 +386,14 @@ def forward_train(p, opts, x, tfd_kps, init_pose, init_scale, K_zoom=None, mean_
         lp_cm = lp_cm and hub is not None
     else:
         pts = _cloud_major_rows(x, tfd_kps)
-        (g, pf), hub = pointnet_rows(pts, p, B, N, M, bool(opts.feature_transform)), None
+        with T.amp_mode("fp32" if enc_fp32 else None):   # (the ops record the mode for their backward)
+            (g, pf), hub = pointnet_rows(pts, p, B, N, M, bool(opts.feature_transform)), None
         fused_rot = lp_cm = False
     # max_n pointfeat (flat_pcl_feat tail) and the rot heads' input in object-major order: [N observed | M prior] per object
     # (CATRE_disR_shared.py:69, :86)
     pfmax, pf_obj = hub if hub is not None else (T.maxpool_points(pf, B, N, M), T.object_major(pf, B, N, M))
 
-    # g (pooled feature, [2B,1024]) has three consumers - its first B rows go to the ts head, all of it to each rotation
+    # g (pooled feature, [2B,out_dim]) has three consumers - its first B rows go to the ts head, all of it to each rotation
     # head - and pfmax one that reads its first B rows: their gradients are summed by one launch each (train_ops._Hub)
     if opts.with_kps_feature or g.shape[0] == B:
         feats = [g[:B], pfmax[:B]] + ([g[B:], pfmax[B:]] if opts.with_kps_feature else [])

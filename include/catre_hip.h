@@ -201,6 +201,32 @@ int catre_trunk(const catre_points* pts, const float* trans3, const float* trans
                 const float* const* params, const float* packed, float* gfeat, float* pointfeat,
                 void* workspace, size_t ws_bytes, int B, int N, int M, void* stream);
 
+/* ---- the encoder at PCLNET.INIT_CFG.out_dim = 64, 128, 256, 512 or 1024 (csrc/catre_trunkw.h) --------------------------
+ * The reference builds conv4 = Conv1d(512, out_dim) (pointnet.py:93); the entry points above read conv4 as [1024,512]
+ * and cannot know another width, so a model with out_dim != 1024 uses the three below for its encoder image and trunk
+ * and never hands its parameters to catre_pack_weights[_sel], catre_trunk, catre_refine_* or catre_train_*_fwd.
+ * The STNs are 1024 wide at any out_dim (pointnet.py:13-78): catre_stn3d_pool / catre_stnkd_pool read this image as is.
+ * Status: CATRE_ERR_BAD_ARG on NULL pointers / non-positive sizes (decided before any HIP call), CATRE_ERR_UNSUPPORTED
+ * for an out_dim outside the set, CATRE_ERR_WORKSPACE when `packed` / `workspace` is short. */
+
+/* Floats of the image catre_pack_encoder_w writes; grows with out_dim; 0 for an out_dim outside the set. */
+size_t catre_packed_floats_w(int out_dim);
+
+/* The fp32 encoder image: what catre_pack_weights_sel(CATRE_PACK_F32_ENCODER) writes for STN3d, STNkd and conv1..conv3
+ * (a NULL source is skipped), and conv4 as out_dim rows of fp32 fragments - exactly out_dim x 512 floats of
+ * params[CATRE_P_CONV4_W] are read (pointnet.py:93,114; layout only, no arithmetic).  The head slots of `params` are
+ * not read. */
+int catre_pack_encoder_w(const float* const* params, int out_dim, float* packed, size_t packed_floats, void* stream);
+
+/* catre_trunk at conv4 width out_dim (pointnet.py:98-116): x T3 -> relu(conv1) -> pointfeat = h1^T T64 (h1 when trans64
+ * is NULL) -> relu(conv2) -> relu(conv3) -> conv4 (no ReLU) -> max over the points, dense fp32 with an exact max-pool.
+ * gfeat [2B, out_dim + 64] = [max_n conv4 | max_n pointfeat], pointfeat as catre_trunk.  `packed`: catre_pack_encoder_w's
+ * image for the same out_dim; `workspace`: catre_workspace_bytes(B,N,M).  Every output equals, bit for bit, what
+ * catre_trunk gives for a 1024-row conv4 whose first out_dim rows are these. */
+int catre_trunk_w(const catre_points* pts, const float* trans3, const float* trans64, const float* const* params,
+                  const float* packed, int out_dim, float* gfeat, float* pointfeat, void* workspace, size_t ws_bytes,
+                  int B, int N, int M, void* stream);
+
 /* Tests only - the error bound of the screened max-pool (kernel-form switch 5, csrc/catre_screen.h): one catre_trunk
  * launch on the screened form of the trunk (full grids only, else CATRE_ERR_UNSUPPORTED; `packed` must hold
  * CATRE_PACK_F32_ENCODER) that also writes, for conv4 and every (tile, channel, point), the split-bf16 screen value and
