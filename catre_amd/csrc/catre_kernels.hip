@@ -1627,6 +1627,8 @@ struct PackLayout {
   // screened max-pool of the fp32 path (catre_screen.h), part of the fp32 encoder pack: hi + lo bf16 fragments of conv4 and
   // its weight-row norms; the same of stn.conv3 and fstn.conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
   size_t scr_c4, scr_nw4, scr_stn_c3, scr_fstn_c3, scr_nw_stn, scr_nw_fstn;
+  // the fp16 screen of the same three layers (`screen_f16`): row-scaled fp16 fragments and the rows' 2^-scale (k_pack_screen_f16)
+  size_t s16_c4, s16_stn_c3, s16_fstn_c3, s16_uw4, s16_uw_stn, s16_uw_fstn;
 };
 
 PackLayout pack_layout(int ts_in) {
@@ -1691,6 +1693,12 @@ PackLayout pack_layout(int ts_in) {
   L.scr_fstn_c3 = take(1024 * 128);
   L.scr_nw_stn = take(1024);
   L.scr_nw_fstn = take(1024);
+  L.s16_c4 = take(1024 * 512 / 2);
+  L.s16_stn_c3 = take(1024 * 128 / 2);
+  L.s16_fstn_c3 = take(1024 * 128 / 2);
+  L.s16_uw4 = take(2 * 1024);  // 2^-scale, then the rows' rounding errors (k_screen_f16_dw)
+  L.s16_uw_stn = take(2 * 1024);
+  L.s16_uw_fstn = take(2 * 1024);
   // everything above is independent of ts_in (the stage entry points rely on that)
   L.ts_w0t = take((size_t)ts_in * 256);
   L.ts_w1t = take(256 * 256);
@@ -1842,12 +1850,14 @@ static int bf_pair_min() {
 // (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl), the
 // pooled replay of the screened kernels (k_trunk4sp / k_stn*_pair_sp, only together with the screens they refine) ON (24.55 vs
 // 28.70 ms, profiles/screen_pool_ab.jsonl), the pooled kernels on runs of tiles with a carried running maximum (k_trunk4sr /
-// k_stn*_pair_sr, only together with the pooled replay they refine) ON (21.59 vs 24.25 ms, profiles/screen_run_ab.jsonl);
+// k_stn*_pair_sr, only together with the pooled replay they refine) ON (21.59 vs 24.25 ms, profiles/screen_run_ab.jsonl),
+// the pooled and run kernels' screen as ONE row-scaled fp16 product instead of three bf16 ones (k_trunk4sp16 / k_trunk4sr16 /
+// k_stn*_pair_sp16 / _sr16, only together with the pooled replay) ON (19.40 vs 21.67 ms, profiles/screen_f16_ab.jsonl);
 // the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
-// CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
+// CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN / CATRE_SCREEN_F16 = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
 // sets the process default once, catre_form_switch changes it at run time.
 enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64,
-       FORM_SCREEN_POOL = 128, FORM_SCREEN_RUN = 256 };
+       FORM_SCREEN_POOL = 128, FORM_SCREEN_RUN = 256, FORM_SCREEN_F16 = 512 };
 #ifndef CATRE_SCREEN_DEFAULT
 #define CATRE_SCREEN_DEFAULT true
 #endif
@@ -1859,6 +1869,9 @@ enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC
 #endif
 #ifndef CATRE_SCREEN_RUN_DEFAULT
 #define CATRE_SCREEN_RUN_DEFAULT true
+#endif
+#ifndef CATRE_SCREEN_F16_DEFAULT
+#define CATRE_SCREEN_F16_DEFAULT true
 #endif
 static std::atomic<int> g_forms{-1};
 static int forms() {
@@ -1873,7 +1886,8 @@ static int forms() {
         (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0) |
         (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0) |
         (on("CATRE_SCREEN_POOL", CATRE_SCREEN_POOL_DEFAULT) ? FORM_SCREEN_POOL : 0) |
-        (on("CATRE_SCREEN_RUN", CATRE_SCREEN_RUN_DEFAULT) ? FORM_SCREEN_RUN : 0);
+        (on("CATRE_SCREEN_RUN", CATRE_SCREEN_RUN_DEFAULT) ? FORM_SCREEN_RUN : 0) |
+        (on("CATRE_SCREEN_F16", CATRE_SCREEN_F16_DEFAULT) ? FORM_SCREEN_F16 : 0);
     g_forms.store(v, std::memory_order_relaxed);
   }
   return v;
@@ -1935,6 +1949,18 @@ static bool screen_run_stn_on() {
   static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_RUN_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_RUN_STN_DEFAULT; }();
   return screen_run_on() && screen_stn_on() && screen_pool_stn_on() && stn;
 }
+// the pooled and run kernels screen with ONE fp16 product instead of the three bf16 ones (k_trunk4sp16 / k_trunk4sr16);
+// refines `screen_pool`
+static bool screen_f16_on() { return (forms() & (FORM_SCREEN_POOL | FORM_SCREEN_F16)) == (FORM_SCREEN_POOL | FORM_SCREEN_F16); }
+// ... and the pooled / run STN pair kernels (k_stn*_pair_sp16 / _sr16).  Its own default so that the two kernel families can
+// follow their own A/B (CATRE_SCREEN_F16_STN_DEFAULT)
+#ifndef CATRE_SCREEN_F16_STN_DEFAULT
+#define CATRE_SCREEN_F16_STN_DEFAULT true
+#endif
+static bool screen_f16_stn_on() {
+  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_F16_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_F16_STN_DEFAULT; }();
+  return screen_f16_on() && screen_pool_stn_on() && stn;
+}
 inline int stn_pair_runs(int B, int N, int M, int SP) {
   return B * ((((N + TP - 1) / TP + 1) / 2 + SP - 1) / SP + (((M + TP - 1) / TP + 1) / 2 + SP - 1) / SP);
 }
@@ -1990,15 +2016,20 @@ void launch_stn3d(const catre_points* pts, const float* const* prm, const float*
 #undef LAUNCH_
   } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
     const int SP = S / 2;
-    hipLaunchKernelGGL(k_stn3d_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
+    const bool f16 = screen_f16_stn_on();
+    hipLaunchKernelGGL(f16 ? k_stn3d_pair_sr16 : k_stn3d_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
                        Stn3dRunArgs{*pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2),
                                     prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm,
-                                    pkb(packed, L.scr_stn_c3), packed + L.scr_nw_stn, B, N, M, SP});
+                                    pkb(packed, f16 ? L.s16_stn_c3 : L.scr_stn_c3), packed + L.scr_nw_stn, B, N, M, SP,
+                                    packed + L.s16_uw_stn});
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    hipLaunchKernelGGL(screen_pool_stn_on() ? k_stn3d_pair_sp : k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
+    const bool f16 = screen_f16_stn_on();
+    hipLaunchKernelGGL(f16 ? k_stn3d_pair_sp16 : screen_pool_stn_on() ? k_stn3d_pair_sp : k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
                        prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
                        prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M,
-                       ScreenArgs{pkb(packed, L.scr_stn_c3), packed + L.scr_nw_stn, probe_s, probe_eps}, probe_rows);
+                       ScreenArgs{pkb(packed, f16 ? L.s16_stn_c3 : L.scr_stn_c3), packed + L.scr_nw_stn, probe_s, probe_eps,
+                                  packed + L.s16_uw_stn},
+                       probe_rows);
   } else if (stn_pair_form(tiles, B, N, M)) {
     const int pairs = stn_pairs(B, N, M);  // (fewer pairs than CUs: one tile per workgroup keeps the whole chip busy)
     hipLaunchKernelGGL(k_stn3d_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B],
@@ -2034,16 +2065,21 @@ void launch_stnkd(const catre_points* pts, const float* trans3, const float* con
 #undef LAUNCH_
   } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
     const int SP = S / 2;
-    hipLaunchKernelGGL(k_stnkd_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
+    const bool f16 = screen_f16_stn_on();
+    hipLaunchKernelGGL(f16 ? k_stnkd_pair_sr16 : k_stnkd_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
                        StnkdRunArgs{*pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1),
                                     prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2), prm[CATRE_P_FSTN_CONV2_B],
                                     pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm,
-                                    pkb(packed, L.scr_fstn_c3), packed + L.scr_nw_fstn, B, N, M, SP});
+                                    pkb(packed, f16 ? L.s16_fstn_c3 : L.scr_fstn_c3), packed + L.scr_nw_fstn, B, N, M, SP,
+                                    packed + L.s16_uw_fstn});
   } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    hipLaunchKernelGGL(screen_pool_stn_on() ? k_stnkd_pair_sp : k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
+    const bool f16 = screen_f16_stn_on();
+    hipLaunchKernelGGL(f16 ? k_stnkd_pair_sp16 : screen_pool_stn_on() ? k_stnkd_pair_sp : k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
                        prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
                        prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
-                       ScreenArgs{pkb(packed, L.scr_fstn_c3), packed + L.scr_nw_fstn, probe_s, probe_eps}, probe_rows);
+                       ScreenArgs{pkb(packed, f16 ? L.s16_fstn_c3 : L.scr_fstn_c3), packed + L.scr_nw_fstn, probe_s, probe_eps,
+                                  packed + L.s16_uw_fstn},
+                       probe_rows);
   } else if (stn_pair_form(tiles, B, N, M)) {
     const int pairs = stn_pairs(B, N, M);
     hipLaunchKernelGGL(k_stnkd_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B],
@@ -2082,17 +2118,21 @@ void launch_trunk(const catre_points* pts, const float* trans3, const float* tra
   } else if (const int S = row_split8(tiles) == 1 && trunk4_on() && screen_on() && screen_run_on() ? screen_run_len(B, N, M) : 1;
              S > 1) {
     const int runs = B * (((N + TP - 1) / TP + S - 1) / S + ((M + TP - 1) / TP + S - 1) / S);
-    hipLaunchKernelGGL(k_trunk4sr, dim3(runs), dim3(256), 0, st,
+    const bool f16 = screen_f16_on();
+    hipLaunchKernelGGL(f16 ? k_trunk4sr16 : k_trunk4sr, dim3(runs), dim3(256), 0, st,
                        TrunkRunArgs{*pts, trans3, trans64, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2),
                                     prm[CATRE_P_CONV2_B], pk4(packed, L.c3), prm[CATRE_P_CONV3_B], pk4(packed, L.c4),
                                     prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, g_trunk_trace,
-                                    ScreenArgs{pkb(packed, L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps}, ws + W.frun,
-                                    B, N, M, S});
+                                    ScreenArgs{pkb(packed, f16 ? L.s16_c4 : L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps,
+                                               packed + L.s16_uw4},
+                                    ws + W.frun, B, N, M, S});
   } else if (row_split8(tiles) == 1 && trunk4_on() && (screen_on() || probe_s)) {
-    hipLaunchKernelGGL(screen_pool_on() ? k_trunk4sp : k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64,
+    const bool f16 = screen_f16_on();
+    hipLaunchKernelGGL(f16 ? k_trunk4sp16 : screen_pool_on() ? k_trunk4sp : k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64,
                        prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
                        prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                       g_trunk_trace, ScreenArgs{pkb(packed, L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps});
+                       g_trunk_trace,
+                       ScreenArgs{pkb(packed, f16 ? L.s16_c4 : L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps, packed + L.s16_uw4});
   } else if (row_split8(tiles) == 1 && trunk4_on()) {
     hipLaunchKernelGGL(k_trunk4<false>, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
                        prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
@@ -2262,17 +2302,32 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     flush_lp(LP_SPLIT);
     hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
                        packed + L.scr_nw4);
+    hipLaunchKernelGGL(k_pack_screen_f16, dim3(1024 * 512 / 256), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
+                       packed + L.scr_nw4, reinterpret_cast<unsigned short*>(packed + L.s16_c4), packed + L.s16_uw4);
+    hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
+                       packed + L.scr_nw4, packed + L.s16_uw4 + 1024);
   }
   // the same of the two STNs' conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
   frag_sp(prm[CATRE_P_STN_CONV3_W], 128, 1024, 128, L.scr_stn_c3);
   frag_sp(prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128, L.scr_fstn_c3);
   flush_lp(LP_SPLIT);
-  if (prm[CATRE_P_STN_CONV3_W])
+  if (prm[CATRE_P_STN_CONV3_W]) {
     hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
                        packed + L.scr_nw_stn);
-  if (prm[CATRE_P_FSTN_CONV3_W])
+    hipLaunchKernelGGL(k_pack_screen_f16, dim3(1024 * 128 / 256), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_stn, reinterpret_cast<unsigned short*>(packed + L.s16_stn_c3), packed + L.s16_uw_stn);
+    hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_stn, packed + L.s16_uw_stn + 1024);
+  }
+  if (prm[CATRE_P_FSTN_CONV3_W]) {
     hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
                        packed + L.scr_nw_fstn);
+    hipLaunchKernelGGL(k_pack_screen_f16, dim3(1024 * 128 / 256), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_fstn, reinterpret_cast<unsigned short*>(packed + L.s16_fstn_c3),
+                       packed + L.s16_uw_fstn);
+    hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
+                       packed + L.scr_nw_fstn, packed + L.s16_uw_fstn + 1024);
+  }
   }
   for (int h = 0; h < 2 && head32; ++h) {
     const int base = h ? CATRE_P_ROTY_L0_W : CATRE_P_ROTX_L0_W;
@@ -2961,7 +3016,7 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 8) return -1;
+  if (id < 0 || id > 9) return -1;
   const int bit = 1 << id;
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);

@@ -47,6 +47,42 @@
 //
 // Replay: GemmPipe::run feeds output (channel c, point p) the products in the order  kc = 0 .. K/8-1, s = 0 .. 3:
 // k = 8 kc + s, then k = 8 kc + 4 + s, starting from 0 - as fmaf (profiles/experiments/screen_mfma_chain.md).
+//
+// The fp16 screen (kernel-form switch `screen_f16`: ScreenPipeF16, ScreenBoundF16, the k_*16 kernels)
+// ---------------------------------------------------------------------------------------------------
+// One v_mfma_f32_32x32x16_f16 product instead of the three bf16 ones: a third of the MFMA issue, one weight stream of half
+// the bytes, four v_cvt_pk_f16_f32 (RNE) per B fragment instead of the hi / lo split.  Selection, list, replay, running
+// maximum and store are the ones above and take eps from this bound; the replay reads the fp32 fragments and the fp32
+// image, so the outputs keep their bits.
+//   Scaling.  fp16 has a 5-bit exponent, so both operands are moved by exact powers of two:
+//     w'_ck = w_ck 2^sw_c, sw_c = min(60, 14 - floor(log2 nw_c))   (pack time, k_pack_screen_f16; uw_c = 2^-sw_c is stored)
+//     a'_k(p) = a_k(p) 2^sa, sa = min(60, 14 - floor(log2 max_p na_p))   (one scale per TILE, screen_tile_scale)
+//   |w_ck| <= nw_c and nw_c 2^sw_c < 2^15, likewise for a: no element exceeds 2^15 < 65504 after rounding - no overflow, and
+//   the largest element of a row is at least 2^14 / sqrt(K).  S' (the accumulator) = 2^(sw + sa) S; the selection evaluates
+//   fl(S -+ eps) as fmaf(S', uw_c 2^-sa, -+eps): the product is exact inside the fma (no rounding even where S would be an
+//   fp32 denormal), so nothing is rounded outside eps's inflation.  One scale per tile is sound because the selection is
+//   absolute; a point far smaller than the tile's largest loses relative accuracy, which delta (below) covers.
+//   sw_c < -60 (nw_c >= 2^75, or not finite) or sa < -60 (a row norm >= 2^75 - in effect 2^64, where screen_row_norms' fp32
+//   sum of squares becomes inf): the scale cannot keep the operand inside fp16.  Such a channel (uw_c = inf) or tile takes EVERY valid point as a candidate - the replay alone is exact - and its
+//   accumulators are ignored.  na_p >= 2^-58 by construction and nw_c = 0 gives sw_c = 60: zero rows need no special case.
+//   Rounding.  fp16 carries 11 significant bits: RNE gives |x~ - x'| <= 2^-11 |x'| for a normal result (half an ulp of an
+//   11-bit significand - not 2^-12).  A result below 2^-14 (fp16-subnormal) may be rounded to a subnormal, flushed by the
+//   conversion or flushed by the matrix pipe; the fp32 multiply by the scale may lose a denormal (2^-126): at most
+//   eta = 2^-13 per element on top of the rounding.
+//   The weights' rounding is KNOWN at pack time: dw_c = ||fp16(w'_c) - w'_c||_2 2^-sw_c (k_screen_f16_dw, summed in double,
+//   rounded up) replaces the worst case 2^-11 nw_c - it measures 0.42 of it on the recipe weights.  The activations' is not (a second
+//   pass over the image per tile would be needed).  With w~ = w' + dw + zeta_w, a~ = a' (1 + theta) + zeta_a, |theta| <=
+//   2^-11, |zeta| <= eta, A' = sum_k |w'| |a'| <= nw' na':
+//     * products:  sum_k |w~ a~ - w' a'| <= (1 + 2^-11) dw' na' + 2^-11 nw' na' + eta (1 + 2^-10) sqrt(K) (nw' + na'(p)) + K eta^2
+//     * w~ a~ is exact in fp32 (22 significant bits) and, where not zero, >= 2^-48: no fp32 underflow in the screen's sums
+//     * screen accumulation: K products, every add may truncate, 17 addends per MFMA:  (17 / 16) K 2u A~, A~ <= A'(1 + 2^-9) + ..
+//     * the fp32 chain Y itself: K u A, and <= K 2^-126 where an fmaf result is flushed
+//   gamma_K = 2^-11 + 2^-21 + 2 K 2^-23  (1.5625 K 2^-23 of accumulation is needed: 28 % left for the second-order terms),
+//   and in the units of S:  delta = 2^-12 sqrt(K) (nw_c 2^-sa + na_p uw_c) + K 2^-24 uw_c 2^-sa + K 2^-122, so
+//     eps_c(p) = ((gamma_K nw_c + (1 + 2^-10) dw_c + rk uw_c) na_p + rk nw_c 2^-sa + K 2^-24 uw_c 2^-sa + K 2^-122) * infl
+//   with rk >= 2^-12 sqrt(K)  (2^-sa <= 2^-14 max_p na_p and uw_c <= 2^-14 nw_c unless clamped: delta is ~ 3e-4 of the gamma
+//   term for the tile's largest point).  infl as above with 2^-19 for the roundings of eps's own operations.
+//   An eps that overflows to +inf makes every point a candidate, as it must.
 #pragma once
 
 template <int K>
@@ -61,6 +97,30 @@ __device__ __forceinline__ void screen_eps_coef(float nw, float& e1, float& e0) 
   e1 = fmaf(ScreenBound<K>::gamma, nw, ScreenBound<K>::delta) * ScreenBound<K>::infl;
   e0 = ScreenBound<K>::delta * (nw + 1.f) * ScreenBound<K>::infl;
 }
+
+// the fp16 screen's bound (see the header)
+template <int K>
+struct ScreenBoundF16 {
+  static_assert(K == 128 || K == 512, "rk is tabulated");
+  static constexpr float gamma = 0x1p-11f + 0x1p-21f + 2.f * K * 0x1p-23f;
+  static constexpr float rk = (K == 128 ? 11.32f : 22.63f) * 0x1p-12f;  // >= 2^-12 sqrt(K)
+  static constexpr float infl = 1.f + 0x1p-22f / gamma + 0x1p-19f;
+};
+// eps = fmaf(e1, na, e0); uw = 2^-sw_c (k_pack_screen_f16), dw = the row's rounding error (k_screen_f16_dw), ua = 2^-sa
+// (screen_tile_scale)
+template <int K>
+__device__ __forceinline__ void screen_eps_coef_f16(float nw, float uw, float dw, float ua, float& e1, float& e0) {
+  typedef ScreenBoundF16<K> SB;
+  e1 = fmaf(SB::gamma, nw, fmaf(1.f + 0x1p-10f, dw, SB::rk * uw)) * SB::infl;
+  e0 = fmaf(SB::rk * nw, ua, fmaf(K * 0x1p-24f * uw, ua, K * 0x1p-122f)) * SB::infl;
+}
+// scale exponent of an operand whose norm bound is n: n 2^s in [2^14, 2^15), at most 60; below -60 the operand cannot be
+// kept inside fp16 (also n = inf / NaN)
+__device__ __forceinline__ int screen_f16_exp(float n) {
+  const int s = 14 - ((int)((__float_as_uint(n) >> 23) & 0xff) - 127);
+  return s > 60 ? 60 : s;
+}
+__device__ __forceinline__ float screen_pow2(int e) { return __uint_as_float((unsigned)(127 + e) << 23); }  // |e| <= 126
 
 // nw[row] >= ||W[row][0:K]||_2: one wave per row, double accumulation, rounded up
 __global__ __launch_bounds__(256) void k_screen_wnorm(const float* __restrict__ W, int ld, int rows, int K,
@@ -77,11 +137,54 @@ __global__ __launch_bounds__(256) void k_screen_wnorm(const float* __restrict__ 
   if (lane == 0) nw[row] = (float)sqrt(s) * (1.f + 0x1p-21f);
 }
 
+// The fp16 screen's weights: row-scaled fp16 fragments in the layout of the bf16 hi fragments (u32x4 index
+// (mb (K / 16) + kc) 64 + lane: row 32 mb + (lane & 31), the 8 values k = 16 kc + 8 (e >> 2) + 4 (lane >> 5) + (e & 3)), and
+// uw[row] = 2^-sw_row (inf: the row cannot be scaled into fp16, its channel takes every point as a candidate).
+// After k_screen_wnorm of the same rows.
+__global__ __launch_bounds__(256) void k_pack_screen_f16(const float* __restrict__ W, int ld, int rows, int K,
+                                                         const float* __restrict__ nw, unsigned short* __restrict__ dst,
+                                                         float* __restrict__ uw) {
+  const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= rows * K) return;
+  const int e = idx & 7, lane = (idx >> 3) & 63, rest = idx >> 9;
+  const int nkc = K / 16;
+  const int kc = rest % nkc, mb = rest / nkc;
+  const int row = mb * 32 + (lane & 31), col = kc * 16 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
+  const int sw = screen_f16_exp(nw[row]);
+  const bool bad = sw < -60;
+  const float w = bad ? 0.f : W[(size_t)row * ld + col] * screen_pow2(sw);
+  dst[idx] = __builtin_bit_cast(unsigned short, (_Float16)w);  // RNE
+  if (col == 0) uw[row] = bad ? INFINITY : screen_pow2(-sw);
+}
+
+// dw[row] >= ||fp16(w') - w'||_2 2^-sw of the row as k_pack_screen_f16 rounds it: one wave per row, double accumulation,
+// rounded up (0 for a row that cannot be scaled: its channel takes every point)
+__global__ __launch_bounds__(256) void k_screen_f16_dw(const float* __restrict__ W, int ld, int rows, int K,
+                                                       const float* __restrict__ nw, float* __restrict__ dw) {
+  const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
+  if (row >= rows) return;
+  const int sw = screen_f16_exp(nw[row]);
+  double s = 0.0;
+  if (sw >= -60) {
+    const float f = screen_pow2(sw);
+    for (int k = lane; k < K; k += 64) {
+      const float w = W[(size_t)row * ld + k] * f;
+      const double r = (double)w - (double)(float)(_Float16)w;
+      s += r * r;
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+  if (lane == 0) dw[row] = sw >= -60 ? (float)(sqrt(s) * (double)screen_pow2(-sw)) * (1.f + 0x1p-21f) : 0.f;
+}
+
 struct ScreenArgs {
   const u32x4* wps;   // hi fragments of the layer ([mb][K/16][lane]), lo fragments rows*K/8 further (k_pack_frag_lp_multi<true>)
+                      // fp16 screen: the scaled fp16 fragments (k_pack_screen_f16)
   const float* nw;    // [rows] weight-row norms (k_screen_wnorm)
   float* probe_s;     // tests only (catre_trunk_screen_probe): [tile][channel][point] screen value and bound, or NULL
   float* probe_eps;
+  const float* uw;    // fp16 screen: [rows] 2^-sw (k_pack_screen_f16), then [rows] dw (k_screen_f16_dw)
 };
 
 #ifdef CATRE_DEBUG_TRACE
@@ -214,6 +317,103 @@ struct ScreenPipe8 {
         if (half == 1 && kc + 1 < NKC) {
 #pragma unroll
           for (int g = 0; g < 24; ++g) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
+            __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // up to three VALU ops behind it
+          }
+        }
+        __builtin_amdgcn_sched_barrier(0);
+        if (half == 1 && kc + 2 < NKC) issue_b(kc + 2);  // braw is free again
+      }
+    }
+  }
+};
+
+// fp16 screen: the tile's scale exponent sa from the row norms na[0 .. 64) (LDS), wave-uniform in a scalar register:
+// max_p na_p 2^sa in [2^14, 2^15), sa <= 60; -61: the tile cannot be scaled into fp16 (a norm >= 2^75 or not finite)
+__device__ __forceinline__ int screen_tile_scale(const float* na, int lane) {
+  float m = na[lane & 63];
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, lane_get(m, lane ^ o));
+  const int s = screen_f16_exp(m);
+  return __builtin_amdgcn_readfirstlane(s < -61 ? -61 : s);
+}
+
+// The fp16 sweep of the same MB8 x NB2 wave tile: ONE product per (m-block, n-block, K = 16 chunk), one weight stream
+// (k_pack_screen_f16), B fragments scaled by 2^sa and rounded to fp16 (RNE) in registers from the same fp32 LDS image.
+// The weight ring works on half chunks as ScreenPipe8's (4 m-blocks x K = 16: now 8 MFMAs = 256 cycles, 16 registers a
+// slot), PFD of them in flight - the registers of the lo stream and of the lo B fragments went into its depth: the L2
+// stream is this sweep's bound.  PRE slots are requested by prefetch() (behind the caller's previous layer, whose epilogue
+// has the registers for no more), the rest at the head of run().
+template <int PFD, int PRE, int NKC_ = 32, bool SWZ = true, int LD = 512>
+struct ScreenPipeF16 {
+  static constexpr int NKC = NKC_, NT = 2 * NKC, RA = PFD + 1;
+  static_assert(PRE <= PFD && PFD < NT, "ring");
+  u32x4 ah[RA][4];
+  const u32x4* wp;
+
+  __device__ __forceinline__ void issue_a(int t) {
+    const int kc = t >> 1, half = t & 1;
+#pragma unroll
+    for (int m = 0; m < 4; ++m) ah[t % RA][m] = wp[((half * 4 + m) * NKC + kc) * 64];
+  }
+  __device__ __forceinline__ void prefetch(const u32x4* __restrict__ wp_) {
+    wp = wp_;
+#pragma unroll
+    for (int d = 0; d < PRE; ++d) issue_a(d);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  __device__ __forceinline__ void run(f32x16 (&acc)[8][2], const float* x, int lane, int sa) {
+    const int n = lane & 31, h = lane >> 5, sw = lane & 15;
+    const float fs = screen_pow2(sa < -60 ? -60 : sa);
+    const float* xrow = x + n * LD;
+    // the k-slot order and the addressing of ScreenPipe8::run
+    const float* xlow[4][2];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+      for (int j = 0; j < 2; ++j) xlow[q][j] = SWZ ? xrow + (((4 * q + 2 * j + h) ^ sw) << 2) : xrow + ((2 * j + h) << 2);
+    f32x4 braw[2][2];
+    u32x4 bh[2][2];  // [chunk parity][nb]
+    auto issue_b = [&](int kc) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+          braw[nb][j] = *reinterpret_cast<const f32x4*>((SWZ ? xlow[kc & 3][j] + (kc >> 2) * 64 : xlow[0][j] + kc * 16) +
+                                                        nb * 32 * LD);
+    };
+    auto cvt_b = [&](int kc) {
+#pragma unroll
+      for (int nb = 0; nb < 2; ++nb) {
+        const float v[8] = {braw[nb][0][0] * fs, braw[nb][0][1] * fs, braw[nb][0][2] * fs, braw[nb][0][3] * fs,
+                            braw[nb][1][0] * fs, braw[nb][1][1] * fs, braw[nb][1][2] * fs, braw[nb][1][3] * fs};
+        bh[kc & 1][nb] = pack8<OpF16>(v);
+      }
+    };
+#pragma unroll
+    for (int d = PRE; d < PFD; ++d) issue_a(d);
+    issue_b(0);
+    cvt_b(0);
+    issue_b(1);
+#pragma unroll
+    for (int kc = 0; kc < NKC; ++kc) {
+#pragma unroll
+      for (int half = 0; half < 2; ++half) {
+        const int t = 2 * kc + half;
+        if (t + PFD < NT) issue_a(t + PFD);
+        __builtin_amdgcn_sched_barrier(0);
+        // second half: scaling and conversion of the NEXT chunk's B fragments (24 VALU ops) ride between this half's MFMAs
+        if (half == 1 && kc + 1 < NKC) cvt_b(kc + 1);
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+          for (int nb = 0; nb < 2; ++nb) {
+            f32x16& c = acc[half * 4 + m][nb];
+            c = OpF16::mfma(bh[kc & 1][nb], ah[t % RA][m], c);
+          }
+        if (half == 1 && kc + 1 < NKC) {
+#pragma unroll
+          for (int g = 0; g < 8; ++g) {
             __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // one MFMA
             __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);  // up to three VALU ops behind it
           }
@@ -512,14 +712,16 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
 //   POOL : the candidates of the wave's MB * 32 = 256 channels are replayed from one list (screen_pool_store); the selection is
 //          the same, `sets` then holds one set per channel at [mb * 32 + n]
 //   RUN  : (POOL only) the run form: frun = the run's running maximum, see screen_pool_store and the header
-template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false, bool RUN = false>
+//   F16  : acc holds the fp16 screen's SCALED values (ScreenPipeF16, tile scale exponent `sa`); see the header
+template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false, bool RUN = false, bool F16 = false>
 __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
                                                     const float* __restrict__ nw, const float* na, const float* x,
                                                     unsigned long long* sets, float* __restrict__ out,
                                                     const float* __restrict__ bias, int ch0, bool relu, int valid, int tile,
                                                     const ScreenArgs& sc, int lane, int ld = K, float* frun = nullptr,
-                                                    bool first = true) {
+                                                    bool first = true, int sa = 0) {
   static_assert(POOL || !RUN, "the run form refines the pooled replay");
+  static_assert(POOL || !F16, "the fp16 screen exists for the pooled forms");
   constexpr int NKC8 = K / 64;
   const int n = lane & 31, h = lane >> 5;
   const int partner = (lane ^ 32) << 2;  // ds_bpermute address of the channel's other half-wave lane
@@ -554,21 +756,35 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
     // candidates of the lane's channel as a 64-bit set: bit 32 h' + 16 nb + r, the same word in both half-waves
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
-      float e1, e0;
-      screen_eps_coef<K>(nw[ch0 + mb * 32 + n], e1, e0);
+      float e1, e0, u = 1.f;  // u: S = u acc (fp16 screen: 2^-(sw + sa), exact)
+      bool all = false;       // fp16 screen: the channel or the tile could not be scaled - every point is a candidate
+      if constexpr (F16) {
+        const float uw = sc.uw[ch0 + mb * 32 + n], ua = screen_pow2(sa < -60 ? 60 : -sa);
+        all = sa < -60 || !(uw <= 0x1p60f);
+        screen_eps_coef_f16<K>(nw[ch0 + mb * 32 + n], uw, sc.uw[1024 + ch0 + mb * 32 + n], ua, e1, e0);
+        u = uw * ua;
+      } else {
+        screen_eps_coef<K>(nw[ch0 + mb * 32 + n], e1, e0);
+      }
       float L = -INFINITY;
       if constexpr (RUN) L = fc[mb];
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) L = fmaxf(L, acc[mb][nb][r] - fmaf(e1, na4[nb][r >> 2][r & 3], e0));
+        for (int r = 0; r < 16; ++r) {
+          const float eps = fmaf(e1, na4[nb][r >> 2][r & 3], e0);
+          L = fmaxf(L, F16 ? fmaf(acc[mb][nb][r], u, -eps) : acc[mb][nb][r] - eps);
+        }
       L = fmaxf(L, swap32(L));
       unsigned own = 0;
 #pragma unroll
       for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
-        for (int r = 0; r < 16; ++r)
-          own |= (acc[mb][nb][r] + fmaf(e1, na4[nb][r >> 2][r & 3], e0) >= L) ? 1u << (nb * 16 + r) : 0u;
+        for (int r = 0; r < 16; ++r) {
+          const float eps = fmaf(e1, na4[nb][r >> 2][r & 3], e0);
+          own |= ((F16 ? fmaf(acc[mb][nb][r], u, eps) : acc[mb][nb][r] + eps) >= L) ? 1u << (nb * 16 + r) : 0u;
+        }
+      if (F16 && all) own = 0xffffffffu;
       own &= vmask;
       if (sc.probe_s) {  // tests only
 #pragma unroll
@@ -576,7 +792,7 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const size_t o = ((size_t)tile * 1024 + ch0 + mb * 32 + n) * TP + nb * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-            sc.probe_s[o] = acc[mb][nb][r];
+            sc.probe_s[o] = F16 ? acc[mb][nb][r] * u : acc[mb][nb][r];
             sc.probe_eps[o] = fmaf(e1, na4[nb][r >> 2][r & 3], e0);
           }
       }
@@ -667,14 +883,20 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
 // k_trunk4 with conv4 512 -> 1024 screened: conv1 .. conv3 and the a3 image are trunk4_body's; the last layer is the
 // split-bf16 screen over all 1024 x 64 outputs and the fp32 replay of the candidates.  Same bits as k_trunk4<false>.
 // ------------------------------------------------------------------------------------------
-template <bool POOL, bool RUN = false>
+template <bool C, class A, class B>
+struct ScreenPipeSel { typedef A type; };
+template <class A, class B>
+struct ScreenPipeSel<false, A, B> { typedef B type; };
+
+template <bool POOL, bool RUN = false, bool F16 = false>
 struct Trunk4ScreenT {
   ScreenArgs sc;
   float* frun;  // run form: the run's 1024 running maxima (workspace), and whether this is the run's first tile
   bool first;
   const f32x4* wf;  // fp32 fragments of the wave's channels (the replay reads them), + (lane & 31)
   const float* b4;
-  ScreenPipe8<2> g4;
+  typename ScreenPipeSel<F16, ScreenPipeF16<5, 2>, ScreenPipe8<2>>::type g4;
+  int sa;  // fp16 screen: the tile's scale exponent (screen_tile_scale), a scalar register across the sweep
   f32x16 acc4[8][2];
   __device__ __forceinline__ void prefetch(const f32x4* __restrict__ wp4, const float* __restrict__ b4_, int mb0, int lane) {
     wf = wp4 + ((size_t)mb0 * 64) * 64 + (lane & 31);
@@ -687,7 +909,12 @@ struct Trunk4ScreenT {
     __syncthreads();
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) acc4[mb][0] = acc4[mb][1] = zero16();
-    g4.run(acc4, a3, lane);
+    if constexpr (F16) {
+      sa = screen_tile_scale(a2, lane);
+      g4.run(acc4, a3, lane, sa);
+    } else {
+      g4.run(acc4, a3, lane);
+    }
   }
   __device__ __forceinline__ void store(const float* a3, float* a2, float* __restrict__ pm, int tile, int mb0, int valid, int,
                                         const TrainSave&, int lane) {
@@ -696,8 +923,8 @@ struct Trunk4ScreenT {
     // the two) - the sweep above runs at exactly 256 VGPRs next to its 256 accumulators, and a lane id live across it is one
     // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-    screen_select_store<8, 512, true, 0, POOL, RUN>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
-                                                    false, valid, tile, sc, lane, 512, frun, first);
+    screen_select_store<8, 512, true, 0, POOL, RUN, F16>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
+                                                         false, valid, tile, sc, lane, 512, frun, first, F16 ? sa : 0);
   }
 };
 typedef Trunk4ScreenT<false> Trunk4Screen;
@@ -717,21 +944,23 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
                      TrainSave{}, tl, blockIdx.x, threadIdx.x);
 }
 
-// the same kernel with the pooled replay (screen_pool_store)
-__global__ __launch_bounds__(256) void k_trunk4sp(catre_points P, const float* __restrict__ trans3,
-                                                  const float* __restrict__ trans64, const float* __restrict__ Wc1,
-                                                  const float* __restrict__ bc1, const f32x4* __restrict__ wp2,
-                                                  const float* __restrict__ b2, const f32x4* __restrict__ wp3,
-                                                  const float* __restrict__ b3, const f32x4* __restrict__ wp4,
-                                                  const float* __restrict__ b4, float* __restrict__ pm,
-                                                  float* __restrict__ pointfeat, int B, int N, int M,
-                                                  unsigned long long* __restrict__ trace, ScreenArgs sc) {
-  __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
-  Trunk4ScreenT<true> tl;
-  tl.sc = sc;
-  trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,
-                     TrainSave{}, tl, blockIdx.x, threadIdx.x);
-}
+// the same kernel with the pooled replay (screen_pool_store); k_trunk4sp16: with the fp16 screen (`screen_f16`)
+#define TRUNK4SP_(NAME, F16)                                                                                              \
+  __global__ __launch_bounds__(256) void NAME(                                                                            \
+      catre_points P, const float* __restrict__ trans3, const float* __restrict__ trans64, const float* __restrict__ Wc1, \
+      const float* __restrict__ bc1, const f32x4* __restrict__ wp2, const float* __restrict__ b2,                         \
+      const f32x4* __restrict__ wp3, const float* __restrict__ b3, const f32x4* __restrict__ wp4,                         \
+      const float* __restrict__ b4, float* __restrict__ pm, float* __restrict__ pointfeat, int B, int N, int M,           \
+      unsigned long long* __restrict__ trace, ScreenArgs sc) {                                                            \
+    __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];                                                       \
+    Trunk4ScreenT<true, false, F16> tl;                                                                                   \
+    tl.sc = sc;                                                                                                           \
+    trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,      \
+                       TrainSave{}, tl, blockIdx.x, threadIdx.x);                                                         \
+  }
+TRUNK4SP_(k_trunk4sp, false)
+TRUNK4SP_(k_trunk4sp16, true)
+#undef TRUNK4SP_
 
 // Run -> tiles.  Runs are enumerated like tiles, observed clouds first; a cloud of T tiles has ceil(T / S) runs of S
 // consecutive tiles, the last one shorter.  No run crosses a cloud.
@@ -769,7 +998,8 @@ struct TrunkRunArgs {
   int B, N, M, S;
 };
 
-__global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
+template <bool F16>
+__device__ __forceinline__ void trunk4sr_body() {
   __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
   // The arguments are read from the kernel-argument segment afresh in every tile (the pointer passes through an empty
   // volatile asm, so the loads cannot leave the loop): held in scalar registers for the whole loop, the 64 dwords of
@@ -778,7 +1008,6 @@ __global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
   // neither threadIdx.x nor anything derived from a lane id is live across a tile's sweep (Trunk4ScreenT::store).
   typedef const __attribute__((address_space(4))) TrunkRunArgs* ArgPtr;
   ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  (void)args;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int tile0, nt;
   run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->S, tile0, nt);
@@ -788,7 +1017,7 @@ __global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const TrunkRunArgs a = *(const TrunkRunArgs*)ap;  // (generic pointer for the copy; the loads stay scalar)
-    Trunk4ScreenT<true, true> tl;
+    Trunk4ScreenT<true, true, F16> tl;
     tl.sc = a.sc;
     tl.frun = a.frun + (size_t)blockIdx.x * 1024;
     tl.first = t == 0;
@@ -796,6 +1025,14 @@ __global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
                        a.B, a.N, a.M, a.trace, TrainSave{}, tl, tile0 + t, wave * 64 + lane);
     __syncthreads();  // the next tile's prologue overwrites the a3 image the other waves still replay from
   }
+}
+__global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
+  (void)args;
+  trunk4sr_body<false>();
+}
+__global__ __launch_bounds__(256) void k_trunk4sr16(TrunkRunArgs args) {  // with the fp16 screen (`screen_f16`)
+  (void)args;
+  trunk4sr_body<true>();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -805,14 +1042,17 @@ __global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
 // The B fragments are split in registers inside every wave, as in the trunk (ScreenPipe8): see DESIGN section 3.
 // ------------------------------------------------------------------------------------------
 typedef ScreenPipe8<2, 8, false, LD128> StnScreenPipe;
+typedef ScreenPipeF16<5, 2, 8, false, LD128> StnScreenPipeF16;  // the fp16 screen (`screen_f16`, k_stn*_pair_sp16 / _sr16)
+template <bool F16>
+using StnPipeT = typename ScreenPipeSel<F16, StnScreenPipeF16, StnScreenPipe>::type;
 
 // scratch: LDS that is dead after conv2 (a1 / h1, 34 KiB): [0, 128) the row norms of both tiles, from float 128 on the
 // waves' candidate sets (4 x 4 KiB).  g holds the first sweep's first weight fragments (requested in front of conv2).
 // probe_rows (tests only): the image rows as [tile][64][128]
 // RUN: the run form (k_stn*_pair_sr) - frun = the 1024 running maxima of the run (LDS, -inf in front of the first tile;
 // first_pair: they are not to be read)
-template <int LAYER, bool POOL, bool RUN = false>
-__device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnScreenPipe& g,
+template <int LAYER, bool POOL, bool RUN = false, bool F16 = false>
+__device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnPipeT<F16>& g,
                                                    const f32x4* __restrict__ wp3, const float* __restrict__ b3,
                                                    float* __restrict__ pm, int tile0, int valid2, const ScreenArgs& sc,
                                                    float* __restrict__ probe_rows, int wave, int tid, int lane,
@@ -833,14 +1073,20 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) acc[mb][0] = acc[mb][1] = zero16();
     const float* x = img + t * TP * LD128;
-    g.run(acc, x, ln);
+    int sa = 0;
+    if constexpr (F16) {
+      sa = screen_tile_scale(scratch + t * TP, ln);
+      g.run(acc, x, ln, sa);
+    } else {
+      g.run(acc, x, ln);
+    }
     // the lane id is computed afresh behind the sweep (see Trunk4Screen::store: the sweep leaves no register for it)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     const f32x4* wf = wp3 + ((size_t)mb0 * 16) * 64 + (ln & 31);
-    screen_select_store<8, 128, false, LAYER, POOL, RUN>(acc, wf, sc.nw, scratch + t * TP, x, sets,
-                                                         pm + (size_t)(tile0 + t) * PMW, b3, mb0 * 32, true,
-                                                         min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128, frun,
-                                                         first_pair && t == 0);
+    screen_select_store<8, 128, false, LAYER, POOL, RUN, F16>(acc, wf, sc.nw, scratch + t * TP, x, sets,
+                                                              pm + (size_t)(tile0 + t) * PMW, b3, mb0 * 32, true,
+                                                              min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128, frun,
+                                                              first_pair && t == 0, sa);
   };
   tile(0, lane);
   if (nt == 2) {  // (again a fresh lane id: nothing lane-dependent of the first tile stays live across its epilogue)
@@ -852,7 +1098,7 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
 
 // POOL: the pooled replay (screen_pool_store) - k_stn3d_pair_sp / k_stnkd_pair_sp
 // (bid, tid): blockIdx.x and threadIdx.x of the one-pair kernels; the run form walks several pairs (RUN, frun, first_pair)
-template <bool POOL, bool RUN = false>
+template <bool POOL, bool RUN = false, bool F16 = false>
 __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* __restrict__ W1,
                                                   const float* __restrict__ b1, const f32x4* __restrict__ wp2,
                                                   const float* __restrict__ b2, const f32x4* __restrict__ wp3,
@@ -880,7 +1126,7 @@ __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* _
     conv3_relu_row<32>(x, y, z, W1, b1, (wave >> 1) * 32, a1 + p * LD64);
   }
   __syncthreads();
-  StnScreenPipe g3;
+  StnPipeT<F16> g3;
   g3.prefetch(sc.wps + ((size_t)wave * 8 * 8) * 64 + lane);
   {
     f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
@@ -888,21 +1134,22 @@ __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, a2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<1, POOL, RUN>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
+  stn_conv3_screened<1, POOL, RUN, F16>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
-#define STN3D_PAIR_S_(NAME, POOL)                                                                                          \
+#define STN3D_PAIR_S_(NAME, POOL, F16)                                                                                        \
   __global__ __launch_bounds__(256) void NAME(catre_points P, const float* __restrict__ W1, const float* __restrict__ b1, \
                                               const f32x4* __restrict__ wp2, const float* __restrict__ b2,                \
                                               const f32x4* __restrict__ wp3, const float* __restrict__ b3,                \
                                               float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,                 \
                                               float* __restrict__ probe_rows) {                                           \
-    stn3d_pair_s_body<POOL>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows, blockIdx.x, threadIdx.x);          \
+    stn3d_pair_s_body<POOL, false, F16>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows, blockIdx.x, threadIdx.x); \
   }
-STN3D_PAIR_S_(k_stn3d_pair_s, false)
-STN3D_PAIR_S_(k_stn3d_pair_sp, true)
+STN3D_PAIR_S_(k_stn3d_pair_s, false, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp, true, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp16, true, true)
 #undef STN3D_PAIR_S_
 
-template <bool POOL, bool RUN = false>
+template <bool POOL, bool RUN = false, bool F16 = false>
 __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* __restrict__ trans3,
                                                   const float* __restrict__ Wc1, const float* __restrict__ bc1,
                                                   const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
@@ -945,7 +1192,7 @@ __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 2, true, false>(acc, f1 + half1 * TP * LD64, LD64, mblk1 * 32, bv1, lane);
   }
   __syncthreads();
-  StnScreenPipe g3;
+  StnPipeT<F16> g3;
   g3.prefetch(sc.wps + ((size_t)wave * 8 * 8) * 64 + lane);
   {
     f32x16 acc[1][4] = {{zero16(), zero16(), zero16(), zero16()}};
@@ -953,19 +1200,20 @@ __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, f2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<2, POOL, RUN>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
+  stn_conv3_screened<2, POOL, RUN, F16>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
-#define STNKD_PAIR_S_(NAME, POOL)                                                                                      \
+#define STNKD_PAIR_S_(NAME, POOL, F16)                                                                                    \
   __global__ __launch_bounds__(256) void NAME(                                                                        \
       catre_points P, const float* __restrict__ trans3, const float* __restrict__ Wc1, const float* __restrict__ bc1, \
       const f32x4* __restrict__ wpf1, const float* __restrict__ bf1, const f32x4* __restrict__ wpf2,                  \
       const float* __restrict__ bf2, const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,                   \
       float* __restrict__ pm, int B, int N, int M, ScreenArgs sc, float* __restrict__ probe_rows) {                   \
-    stnkd_pair_s_body<POOL>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows,       \
+    stnkd_pair_s_body<POOL, false, F16>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows, \
                             blockIdx.x, threadIdx.x);                                                                  \
   }
-STNKD_PAIR_S_(k_stnkd_pair_s, false)
-STNKD_PAIR_S_(k_stnkd_pair_sp, true)
+STNKD_PAIR_S_(k_stnkd_pair_s, false, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp, true, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp16, true, true)
 #undef STNKD_PAIR_S_
 
 // ------------------------------------------------------------------------------------------
@@ -1000,13 +1248,14 @@ struct Stn3dRunArgs {
   const u32x4* wps;  // ScreenArgs without the probes: the probe calls keep the one-pair kernels
   const float* nw;
   int B, N, M, SP;
+  const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
 };
 
-__global__ __launch_bounds__(256) void k_stn3d_pair_sr(Stn3dRunArgs args) {
+template <bool F16>
+__device__ __forceinline__ void stn3d_pair_sr_body() {
   __shared__ __attribute__((aligned(16))) float frun[1024];
   typedef const __attribute__((address_space(4))) Stn3dRunArgs* ArgPtr;
   ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  (void)args;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int pair0, np;
   pair_run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->SP, pair0, np);
@@ -1019,10 +1268,19 @@ __global__ __launch_bounds__(256) void k_stn3d_pair_sr(Stn3dRunArgs args) {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const Stn3dRunArgs a = *(const Stn3dRunArgs*)ap;
-    stn3d_pair_s_body<true, true>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
-                                  ScreenArgs{a.wps, a.nw, nullptr, nullptr}, nullptr, bid, wave * 64 + lane, frun, false);
+    stn3d_pair_s_body<true, true, F16>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
+                                       ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane, frun,
+                                       false);
     __syncthreads();  // the next pair's conv1 overwrites the candidate sets, its conv2 the image the other waves replay from
   }
+}
+__global__ __launch_bounds__(256) void k_stn3d_pair_sr(Stn3dRunArgs args) {
+  (void)args;
+  stn3d_pair_sr_body<false>();
+}
+__global__ __launch_bounds__(256) void k_stn3d_pair_sr16(Stn3dRunArgs args) {
+  (void)args;
+  stn3d_pair_sr_body<true>();
 }
 
 struct StnkdRunArgs {
@@ -1038,13 +1296,14 @@ struct StnkdRunArgs {
   const u32x4* wps;  // ScreenArgs without the probes: the probe calls keep the one-pair kernels
   const float* nw;
   int B, N, M, SP;
+  const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
 };
 
-__global__ __launch_bounds__(256) void k_stnkd_pair_sr(StnkdRunArgs args) {
+template <bool F16>
+__device__ __forceinline__ void stnkd_pair_sr_body() {
   __shared__ __attribute__((aligned(16))) float frun[1024];
   typedef const __attribute__((address_space(4))) StnkdRunArgs* ArgPtr;
   ArgPtr ap = (ArgPtr)__builtin_amdgcn_kernarg_segment_ptr();
-  (void)args;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int pair0, np;
   pair_run_info(blockIdx.x, ap->B, ap->N, ap->M, ap->SP, pair0, np);
@@ -1057,8 +1316,17 @@ __global__ __launch_bounds__(256) void k_stnkd_pair_sr(StnkdRunArgs args) {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const StnkdRunArgs a = *(const StnkdRunArgs*)ap;
-    stnkd_pair_s_body<true, true>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N, a.M,
-                                  ScreenArgs{a.wps, a.nw, nullptr, nullptr}, nullptr, bid, wave * 64 + lane, frun, false);
+    stnkd_pair_s_body<true, true, F16>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N,
+                                       a.M, ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane,
+                                       frun, false);
     __syncthreads();
   }
+}
+__global__ __launch_bounds__(256) void k_stnkd_pair_sr(StnkdRunArgs args) {
+  (void)args;
+  stnkd_pair_sr_body<false>();
+}
+__global__ __launch_bounds__(256) void k_stnkd_pair_sr16(StnkdRunArgs args) {
+  (void)args;
+  stnkd_pair_sr_body<true>();
 }

@@ -285,7 +285,7 @@ def bump_param_epoch():
 
 
 FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7,
-            "screen_run": 8}
+            "screen_run": 8, "screen_f16": 9}
 
 
 def form_switch(name, value=None):

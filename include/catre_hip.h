@@ -345,10 +345,16 @@ int catre_profile_enable(int kernel_id, int max_records);
  * it - same bits; likewise the pooled STN pair kernels as k_stn3d_pair_sr / k_stnkd_pair_sr on runs of S / 2 pairs (their
  * own arm: CATRE_SCREEN_RUN_STN = 0, read once per process, leaves them on one pair); it refines 7 and so 5;
  * catre_trunk_screen_probe follows it, catre_stn_screen_probe keeps the one-pair kernels),
+ * 9: the pooled and run kernels screen with ONE row-scaled fp16 product per chunk instead of three bf16 ones (a third of
+ * the MFMA issue, half the weight stream, a wider error bound and so more replayed points), k_trunk4sp16 / k_trunk4sr16 -
+ * same bits for finite activations, the caveat of 5 holds; tiles or weight rows whose norm is 2^75 or more (activations: a
+ * sum of squares past the fp32 range) cannot be scaled into fp16 and replay every point; likewise k_stn3d_pair_sp16 / _sr16
+ * and k_stnkd_pair_sp16 / _sr16 (their own arm: CATRE_SCREEN_F16_STN = 0, read once per process, leaves the STN kernels on
+ * the split-bf16 screen); it refines 7 and so 5; both probes follow it and return the fp16 screen value and its bound,
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
- * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-8 on, 3 and 4 off -
+ * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-9 on, 3 and 4 off -
  * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
- * CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN = 0,
+ * CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN / CATRE_SCREEN_F16 = 0,
  * CATRE_ROTW / CATRE_FC_TAIL = 1); calls in flight keep the form they were
  * launched with. */
 int catre_form_switch(int id, int value);

@@ -3,7 +3,9 @@
 for the per-channel replay) the kernels that replay from one list per wave report list entries and rounds of 64 per
 (wave, tile) instead of trips per 32-channel block.  With `screen_run` on (the default; CATRE_SCREEN_RUN=0 for one tile per
 workgroup, CATRE_SCREEN_RUN_STN=0 for the trunk alone) a workgroup carries the running maximum over a run of tiles: fewer
-entries, channels without a candidate (bin 0) and (wave, tile) units whose list is empty.
+entries, channels without a candidate (bin 0) and (wave, tile) units whose list is empty.  With `screen_f16` on (the default;
+CATRE_SCREEN_F16=0 for the split-bf16 screen, CATRE_SCREEN_F16_STN=0 for the trunk alone) the pooled and run kernels screen
+with one fp16 product: a wider eps, more entries.
 
 Needs the instrumented library (`make -C catre_amd/csrc TRACE=1`), whose screened kernels count while they run:
     CATRE_HIP_LIB=catre_amd/csrc/libcatre_hip_trace.so python profiles/screen_candidates.py [out.txt]
@@ -39,9 +41,12 @@ hip.check(lib.catre_debug_screen_counts(cnt, 1), "catre_debug_screen_counts")
 pool = hip.form_switch("screen_pool")
 run = pool and hip.form_switch("screen_run")
 run_stn = run and os.environ.get("CATRE_SCREEN_RUN_STN", "1") != "0"
+f16 = pool and hip.form_switch("screen_f16")
+f16_stn = f16 and os.environ.get("CATRE_SCREEN_F16_STN", "1") != "0"
 S = (hip.screen_run_len() or hip.screen_run_rule(B, N, M, torch.cuda.get_device_properties(0).multi_processor_count)) if run else 1
 lines = [f"B={B} N=M={N} K={K} refine, make_inputs(seed=1000), recipe weights; screen_pool {'on' if pool else 'off'}; "
          f"screen_run {'on, run length ' + str(S) + (' (STN kernels: ' + ('on' if run_stn else 'off') + ')') if run and S > 1 else 'off'}; "
+         f"screen_f16 {'on (STN kernels: ' + ('on' if f16_stn else 'off') + ')' if f16 else 'off'}; "
          "per-channel replay: chains a lane carries at once: 4"]
 for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_s)", "fstn.conv3 (k_stnkd_pair_s)")):
     c = list(cnt)[64 * row:64 * row + 64]
@@ -50,6 +55,8 @@ for row, name in enumerate(("trunk conv4 (k_trunk4s)", "stn.conv3 (k_stn3d_pair_
         name = name.replace("_s)", "_sp)").replace("k_trunk4s", "k_trunk4sp")
         if run and S > 1 and (row == 0 or run_stn):
             name = name.replace("sp)", "sr)")
+        if f16 and (row == 0 or f16_stn):
+            name = name.replace(")", "16)")
     lines.append(f"screened {name}")
     tot = sum(c[:32])
     mean = sum(i * v for i, v in enumerate(c[:32])) / max(tot, 1)
