@@ -1612,99 +1612,10 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 // ==========================================================================================
 // host side: packed-weight and workspace layouts, launchers, C ABI
 // ==========================================================================================
+#include "catre_forms.h"  // the switch table, the form decision, PackLayout and the stages' weight bundles (no HIP in there)
+using namespace catre_host;
+static_assert(TILE == TP, "catre_forms.h counts tiles of TP points");
 namespace {
-
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
-
-struct PackLayout {
-  size_t stn_c2, stn_c3, fstn_c1, fstn_c2, fstn_c3, c2, c3, c4, rot_l0[2], rot_l1[2], ts_w0t, ts_w1t, sumwp, total;
-  // bf16 fragment packs of the same matrices (catre_bf16.h), offsets in floats
-  size_t bf_stn_c2, bf_stn_c3, bf_fstn_c1, bf_fstn_c2, bf_fstn_c3, bf_c2, bf_c3, bf_c4, bf_rot_l0[2], bf_rot_l1[2];
-  // hi + lo bf16 fragment packs of the three split-mode layers (catre_split.h), offsets in floats
-  size_t sp_stn_c2, sp_stn_c3, sp_fstn_c1, sp_fstn_c2, sp_fstn_c3, sp_c3, sp_c4, sp_rot_l0[2], sp_rot_l1[2];
-  // fp16 fragment packs of the bf16 packs' matrices, same layout (CATRE_PACK_F16, CATRE_DTYPE_F16), offsets in floats
-  size_t f16_stn_c2, f16_stn_c3, f16_fstn_c1, f16_fstn_c2, f16_fstn_c3, f16_c2, f16_c3, f16_c4, f16_rot_l0[2], f16_rot_l1[2];
-  // screened max-pool of the fp32 path (catre_screen.h), part of the fp32 encoder pack: hi + lo bf16 fragments of conv4 and
-  // its weight-row norms; the same of stn.conv3 and fstn.conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
-  size_t scr_c4, scr_nw4, scr_stn_c3, scr_fstn_c3, scr_nw_stn, scr_nw_fstn;
-  // the fp16 screen of the same three layers (`screen_f16`): row-scaled fp16 fragments and the rows' 2^-scale (k_pack_screen_f16)
-  size_t s16_c4, s16_stn_c3, s16_fstn_c3, s16_uw4, s16_uw_stn, s16_uw_fstn;
-};
-
-PackLayout pack_layout(int ts_in) {
-  PackLayout L;
-  size_t o = 0;
-  auto take = [&](size_t n) {
-    size_t r = o;
-    o += align_up(n, 64);
-    return r;
-  };
-  L.stn_c2 = take(128 * 64);
-  L.stn_c3 = take(1024 * 128);
-  L.fstn_c1 = take(64 * 64);
-  L.fstn_c2 = take(128 * 64);
-  L.fstn_c3 = take(1024 * 128);
-  L.c2 = take(128 * 64);
-  L.c3 = take(512 * 128);
-  L.c4 = take(1024 * 512);
-  for (int h = 0; h < 2; ++h) {
-    L.rot_l0[h] = take(256 * 64);
-    L.rot_l1[h] = take(256 * 256);
-  }
-  L.sumwp = take(64);
-  L.bf_stn_c2 = take(128 * 64 / 2);
-  L.bf_stn_c3 = take(1024 * 128 / 2);
-  L.bf_fstn_c1 = take(64 * 64 / 2);
-  L.bf_fstn_c2 = take(128 * 64 / 2);
-  L.bf_fstn_c3 = take(1024 * 128 / 2);
-  L.bf_c2 = take(128 * 64 / 2);
-  L.bf_c3 = take(512 * 128 / 2);
-  L.bf_c4 = take(1024 * 512 / 2);
-  for (int h = 0; h < 2; ++h) {
-    L.bf_rot_l0[h] = take(256 * 64 / 2);
-    L.bf_rot_l1[h] = take(256 * 256 / 2);
-  }
-  L.sp_stn_c2 = take(128 * 64);
-  L.sp_stn_c3 = take(1024 * 128);
-  L.sp_fstn_c1 = take(64 * 64);
-  L.sp_fstn_c2 = take(128 * 64);
-  L.sp_fstn_c3 = take(1024 * 128);
-  L.sp_c3 = take(512 * 128);
-  L.sp_c4 = take(1024 * 512);
-  for (int h = 0; h < 2; ++h) {
-    L.sp_rot_l0[h] = take(256 * 64);
-    L.sp_rot_l1[h] = take(256 * 256);
-  }
-  L.f16_stn_c2 = take(128 * 64 / 2);
-  L.f16_stn_c3 = take(1024 * 128 / 2);
-  L.f16_fstn_c1 = take(64 * 64 / 2);
-  L.f16_fstn_c2 = take(128 * 64 / 2);
-  L.f16_fstn_c3 = take(1024 * 128 / 2);
-  L.f16_c2 = take(128 * 64 / 2);
-  L.f16_c3 = take(512 * 128 / 2);
-  L.f16_c4 = take(1024 * 512 / 2);
-  for (int h = 0; h < 2; ++h) {
-    L.f16_rot_l0[h] = take(256 * 64 / 2);
-    L.f16_rot_l1[h] = take(256 * 256 / 2);
-  }
-  L.scr_c4 = take(1024 * 512);
-  L.scr_nw4 = take(1024);
-  L.scr_stn_c3 = take(1024 * 128);
-  L.scr_fstn_c3 = take(1024 * 128);
-  L.scr_nw_stn = take(1024);
-  L.scr_nw_fstn = take(1024);
-  L.s16_c4 = take(1024 * 512 / 2);
-  L.s16_stn_c3 = take(1024 * 128 / 2);
-  L.s16_fstn_c3 = take(1024 * 128 / 2);
-  L.s16_uw4 = take(2 * 1024);  // 2^-scale, then the rows' rounding errors (k_screen_f16_dw)
-  L.s16_uw_stn = take(2 * 1024);
-  L.s16_uw_fstn = take(2 * 1024);
-  // everything above is independent of ts_in (the stage entry points rely on that)
-  L.ts_w0t = take((size_t)ts_in * 256);
-  L.ts_w1t = take(256 * 256);
-  L.total = o;
-  return L;
-}
 
 struct WsLayout {
   size_t tspart, xbuf, kbuf, pm, pool, h1, h2, trans3, trans64, gfeat, pointfeat, dt, ds, rot6d, bias0, gn0, gn1, aff0, gn1stat, y1, rpart,
@@ -1759,17 +1670,14 @@ inline bool dims_ok(int B, int N, int M) { return B > 0 && N > 0 && M > 0; }
 // the PointNet stages also run on a single cloud per object (M == 0: PointNetfeat.forward on its own)
 inline bool dims_ok1(int B, int N, int M) { return B > 0 && N > 0 && M >= 0; }
 inline int n_clouds(int B, int M) { return M > 0 ? 2 * B : B; }
-// workgroups per 64-point tile of the encoder kernels: small grids split a tile's output channels over 2 or 4
-// workgroups as long as that still fits one wave of workgroups on the 256 CUs
-// RS_DISPATCH(rs, L): expands the launch macro L(RS) for the compile-time RS matching rs
+// RS_DISPATCH(rs, L): expands the launch macro L(RS) for the compile-time RS matching rs (row_split, catre_forms.h)
 #define RS_DISPATCH(rs, L) \
   switch (rs) {            \
     case 4: L(4); break;   \
     case 2: L(2); break;   \
     default: L(1);         \
   }
-inline int row_split(int tiles) { return tiles * 4 <= 256 ? 4 : tiles * 2 <= 256 ? 2 : 1; }
-// the fp32 encoder kernels also come with eight workgroups per tile (a single object: 32 tiles on 256 CUs)
+// the fp32 encoder kernels also come with eight workgroups per tile (row_split8)
 #define RS_DISPATCH8(rs, L) \
   switch (rs) {             \
     case 8: L(8); break;    \
@@ -1777,7 +1685,6 @@ inline int row_split(int tiles) { return tiles * 4 <= 256 ? 4 : tiles * 2 <= 256
     case 2: L(2); break;    \
     default: L(1);          \
   }
-inline int row_split8(int tiles) { return tiles * 8 <= 256 ? 8 : row_split(tiles); }
 // workgroups per object of k_gn0_from_moments (catre_gram.h): its 8 (head, channel block) combinations on 8 / 4 / 2 / 1
 inline int gn0_shares(int B) { return B * 8 <= 512 ? 8 : B * 4 <= 512 ? 4 : B * 2 <= 512 ? 2 : 1; }
 // workgroups per HALF tile of k_trunk_h (0: too many tiles for it)
@@ -1832,92 +1739,6 @@ struct ProfState {
 ProfState g_prof;
 unsigned long long* g_trunk_trace = nullptr;  // catre_debug_trunk_trace
 
-// Smallest grid (in PAIRS of tiles) that takes the 128-point bf16 trunk; read once (CATRE_BF_PAIR_MIN overrides it for A/B
-// measurements: 0 = always, a huge value = never).  512 pairs = two workgroups for each of the 256 CUs.
-static int bf_pair_min() {
-  static const int v = [] {
-    const char* e = getenv("CATRE_BF_PAIR_MIN");
-    return e ? atoi(e) : 512;
-  }();
-  return v;
-}
-
-// Which kernel FORM a full grid takes where more than one exists (all forms of a stage give the same bits; the switches
-// exist for A/B measurements and for tests that compare the forms in one process).  Defaults: the encoder forms on,
-// k_rot_l1w OFF (it measured 8 % slower than k_rot_l1<1>: profiles/r06_rotw_phases.txt), k_fc_tail OFF (one object:
-// 0.643 vs 0.620 ms per K = 4 refine, profiles/r06_fc_tail_ab.jsonl), the screened conv4 max-pool k_trunk4s ON (30.7 vs 34.0 ms
-// per K = 4 refine at B = 256, profiles/screen_ab.jsonl), the screened conv3 max-pool of the STN pair kernels
-// (k_stn3d_pair_s / k_stnkd_pair_s, only together with FORM_SCREEN) ON (28.97 vs 30.82 ms, profiles/screen_stn_ab.jsonl), the
-// pooled replay of the screened kernels (k_trunk4sp / k_stn*_pair_sp, only together with the screens they refine) ON (24.55 vs
-// 28.70 ms, profiles/screen_pool_ab.jsonl), the pooled kernels on runs of tiles with a carried running maximum (k_trunk4sr /
-// k_stn*_pair_sr, only together with the pooled replay they refine) ON (21.59 vs 24.25 ms, profiles/screen_run_ab.jsonl),
-// the pooled and run kernels' screen as ONE row-scaled fp16 product instead of three bf16 ones (k_trunk4sp16 / k_trunk4sr16 /
-// k_stn*_pair_sp16 / _sr16, only together with the pooled replay) ON (19.40 vs 21.67 ms, profiles/screen_f16_ab.jsonl);
-// the environment (CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
-// CATRE_SCREEN_STN / CATRE_SCREEN_POOL / CATRE_SCREEN_RUN / CATRE_SCREEN_F16 = 0, CATRE_ROTW / CATRE_FC_TAIL = 1)
-// sets the process default once, catre_form_switch changes it at run time.
-enum { FORM_TRUNK4 = 1, FORM_STN4 = 2, FORM_STN_PAIR = 4, FORM_ROTW = 8, FORM_FC_TAIL = 16, FORM_SCREEN = 32, FORM_SCREEN_STN = 64,
-       FORM_SCREEN_POOL = 128, FORM_SCREEN_RUN = 256, FORM_SCREEN_F16 = 512 };
-#ifndef CATRE_SCREEN_DEFAULT
-#define CATRE_SCREEN_DEFAULT true
-#endif
-#ifndef CATRE_SCREEN_STN_DEFAULT
-#define CATRE_SCREEN_STN_DEFAULT true
-#endif
-#ifndef CATRE_SCREEN_POOL_DEFAULT
-#define CATRE_SCREEN_POOL_DEFAULT true
-#endif
-#ifndef CATRE_SCREEN_RUN_DEFAULT
-#define CATRE_SCREEN_RUN_DEFAULT true
-#endif
-#ifndef CATRE_SCREEN_F16_DEFAULT
-#define CATRE_SCREEN_F16_DEFAULT true
-#endif
-static std::atomic<int> g_forms{-1};
-static int forms() {
-  int v = g_forms.load(std::memory_order_relaxed);
-  if (v < 0) {
-    auto on = [](const char* name, bool dflt = true) {
-      const char* e = getenv(name);
-      return e ? atoi(e) != 0 : dflt;
-    };
-    v = (on("CATRE_TRUNK4") ? FORM_TRUNK4 : 0) | (on("CATRE_STN4") ? FORM_STN4 : 0) |
-        (on("CATRE_STN_PAIR") ? FORM_STN_PAIR : 0) | (on("CATRE_ROTW", false) ? FORM_ROTW : 0) |
-        (on("CATRE_FC_TAIL", false) ? FORM_FC_TAIL : 0) | (on("CATRE_SCREEN", CATRE_SCREEN_DEFAULT) ? FORM_SCREEN : 0) |
-        (on("CATRE_SCREEN_STN", CATRE_SCREEN_STN_DEFAULT) ? FORM_SCREEN_STN : 0) |
-        (on("CATRE_SCREEN_POOL", CATRE_SCREEN_POOL_DEFAULT) ? FORM_SCREEN_POOL : 0) |
-        (on("CATRE_SCREEN_RUN", CATRE_SCREEN_RUN_DEFAULT) ? FORM_SCREEN_RUN : 0) |
-        (on("CATRE_SCREEN_F16", CATRE_SCREEN_F16_DEFAULT) ? FORM_SCREEN_F16 : 0);
-    g_forms.store(v, std::memory_order_relaxed);
-  }
-  return v;
-}
-static bool trunk4_on() { return forms() & FORM_TRUNK4; }  // one-wave-per-SIMD trunk (k_trunk4); off: the 8-wave kernel
-inline int stn_pairs(int B, int N, int M) { return B * (((N + TP - 1) / TP + 1) / 2 + ((M + TP - 1) / TP + 1) / 2); }
-static bool stn_pair_on() { return forms() & FORM_STN_PAIR; }  // off: one tile per workgroup
-static bool stn4_on() { return forms() & FORM_STN4; }
-static bool fc_tail_on() { return forms() & FORM_FC_TAIL; }  // B <= 8: an FC tail as one launch (k_fc_tail); off (default: the fused form measured SLOWER, profiles/r06_fc_tail_ab.jsonl): three k_linear launches
-static bool screen_on() { return forms() & FORM_SCREEN; }  // fp32 full grids: conv4's max-pool screened on the bf16 pipe (k_trunk4s)
-// fp32 full-grid STN pair kernels: conv3's max-pool screened (k_stn*_pair_s); refines `screen`: CATRE_SCREEN = 0 turns both off
-static bool screen_stn_on() { return (forms() & (FORM_SCREEN | FORM_SCREEN_STN)) == (FORM_SCREEN | FORM_SCREEN_STN); }
-// the screened kernels replay their candidates from one list per wave (k_trunk4sp); refines `screen`
-static bool screen_pool_on() { return forms() & FORM_SCREEN_POOL; }
-// the pooled trunk walks runs of tiles of one cloud and carries the running maximum (k_trunk4sr); refines `screen_pool`
-static bool screen_run_on() { return (forms() & (FORM_SCREEN_POOL | FORM_SCREEN_RUN)) == (FORM_SCREEN_POOL | FORM_SCREEN_RUN); }
-// Run length of k_trunk4sr.  One workgroup fits a CU, so a grid of R workgroups that each walk up to S tiles takes
-// ceil(R / cus) * S tile slots.  The rule: the largest S <= 16 that takes no more slots than the one-tile grid's
-// ceil(tiles / cus) - its last round is then as full as the one-tile grid's - else 1, the one-tile kernel k_trunk4sp.
-// (B = 256, N = M = 1024 on 256 CUs: 16; B = 128: 16; B = 64: 8; B = 200: 1.)
-static std::atomic<int> g_run_len{0};  // catre_screen_run_len: > 0 forces the length
-static int screen_run_rule(int B, int N, int M, int cus) {
-  const int TN = (N + TP - 1) / TP, TM = (M + TP - 1) / TP;
-  const long long slots1 = ((long long)B * (TN + TM) + cus - 1) / cus;
-  for (int S = 16; S > 1; --S) {
-    const long long R = (long long)B * ((TN + S - 1) / S + (TM + S - 1) / S);
-    if ((R + cus - 1) / cus * S <= slots1) return S;
-  }
-  return 1;
-}
 static int device_cus() {
   static const int n = [] {
     int dev = 0, v = 0;
@@ -1927,44 +1748,14 @@ static int device_cus() {
   }();
   return n;
 }
-static int screen_run_len(int B, int N, int M) {
-  const int f = g_run_len.load(std::memory_order_relaxed);
-  return f > 0 ? f : screen_run_rule(B, N, M, device_cus());
+static bool form_on(int id) { return effective_forms(forms()) >> id & 1; }
+// the form one launch takes (form_decision of catre_forms.h on this process's switches); CATRE_OK or the status to return
+static int decide(int stage, int mode, bool save, bool rows, bool probe, int B, int N, int M, FormDecision* d) {
+  if (!form_decision(stage, mode, save, rows, probe, B, N, M, effective_forms(forms()), device_cus(),
+                     g_run_len.load(std::memory_order_relaxed), bf_pair_min(), d))
+    return CATRE_ERR_BAD_ARG;
+  return d->form == CATRE_FORM_UNSUPPORTED ? CATRE_ERR_UNSUPPORTED : CATRE_OK;
 }
-// ... and the STN pair kernels (k_stn*_pair_sp): with `screen_stn` as well.  Its own default so that the two kernel families
-// can follow their own A/B (CATRE_SCREEN_POOL_STN_DEFAULT)
-#ifndef CATRE_SCREEN_POOL_STN_DEFAULT
-#define CATRE_SCREEN_POOL_STN_DEFAULT true
-#endif
-static bool screen_pool_stn_on() {
-  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_POOL_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_POOL_STN_DEFAULT; }();
-  return screen_pool_on() && stn;
-}
-// ... and the pooled STN pair kernels as k_stn*_pair_sr, runs of S / 2 pairs.  Its own default so that the two kernel
-// families can follow their own A/B (CATRE_SCREEN_RUN_STN_DEFAULT)
-#ifndef CATRE_SCREEN_RUN_STN_DEFAULT
-#define CATRE_SCREEN_RUN_STN_DEFAULT true
-#endif
-static bool screen_run_stn_on() {
-  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_RUN_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_RUN_STN_DEFAULT; }();
-  return screen_run_on() && screen_stn_on() && screen_pool_stn_on() && stn;
-}
-// the pooled and run kernels screen with ONE fp16 product instead of the three bf16 ones (k_trunk4sp16 / k_trunk4sr16);
-// refines `screen_pool`
-static bool screen_f16_on() { return (forms() & (FORM_SCREEN_POOL | FORM_SCREEN_F16)) == (FORM_SCREEN_POOL | FORM_SCREEN_F16); }
-// ... and the pooled / run STN pair kernels (k_stn*_pair_sp16 / _sr16).  Its own default so that the two kernel families can
-// follow their own A/B (CATRE_SCREEN_F16_STN_DEFAULT)
-#ifndef CATRE_SCREEN_F16_STN_DEFAULT
-#define CATRE_SCREEN_F16_STN_DEFAULT true
-#endif
-static bool screen_f16_stn_on() {
-  static const bool stn = [] { const char* e = getenv("CATRE_SCREEN_F16_STN"); return e ? atoi(e) != 0 : CATRE_SCREEN_F16_STN_DEFAULT; }();
-  return screen_f16_on() && screen_pool_stn_on() && stn;
-}
-inline int stn_pair_runs(int B, int N, int M, int SP) {
-  return B * ((((N + TP - 1) / TP + 1) / 2 + SP - 1) / SP + (((M + TP - 1) / TP + 1) / 2 + SP - 1) / SP);
-}
-static bool rotw_on() { return forms() & FORM_ROTW; }  // rotation heads, one wave per SIMD (k_rot_l1w); off (default): k_rot_l1<1>
 
 // The measurement hooks are the library's only process-global mutable state.  They are fenced: compiled out entirely
 // with -DCATRE_NO_PROFILING (catre_profile_* then return CATRE_ERR_UNSUPPORTED), off unless catre_profile_enable was
@@ -1994,159 +1785,122 @@ struct ProfScope {
 };
 #endif
 
+// what every kernel of an encoder stage is handed besides its weights
+struct EncCall {
+  const catre_points* pts;
+  const float *trans3, *trans64;  // STNkd: trans3; trunk: both
+  float* pm;                      // tile partial maxima (ws + W.pm)
+  int B, N, M;
+  hipStream_t st;
+};
+// the positional arguments every kernel form of a stage starts with: call c, weight bundle w (catre_forms.h)
+#define STN3D_ARGS(c, w) *(c).pts, (w).w1, (w).b1, (w).w2, (w).b2, (w).w3, (w).b3, (c).pm, (c).B, (c).N, (c).M
+#define STNKD_ARGS(c, w) \
+  *(c).pts, (c).trans3, (w).wc1, (w).bc1, (w).w1, (w).b1, (w).w2, (w).b2, (w).w3, (w).b3, (c).pm, (c).B, (c).N, (c).M
+#define TRUNK_ARGS(c, w, pointfeat)                                                                                        \
+  *(c).pts, (c).trans3, (c).trans64, (w).w1, (w).b1, (w).w2, (w).b2, (w).w3, (w).b3, (w).w4, (w).b4, (c).pm, pointfeat, (c).B, \
+      (c).N, (c).M
+inline bool f16_screen(const FormDecision& d) { return d.form == CATRE_FORM_RUN_F16 || d.form == CATRE_FORM_SCREEN_F16; }
 
-// full grids: the STN kernels on pairs of tiles
-static bool stn_pair_form(int tiles, int B, int N, int M) {
-  return row_split8(tiles) == 1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256;
-}
-
-// The three encoder kernels of one iteration (fp32 or split compute), tile partial maxima -> ws + W.pm
-void launch_stn3d(const catre_points* pts, const float* const* prm, const float* packed, float* ws, const WsLayout& W,
-                  int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr, float* probe_s = nullptr,
-                  float* probe_eps = nullptr, float* probe_rows = nullptr) {
-  const PackLayout L = pack_layout(1);  // conv offsets do not depend on ts_in
-  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-  ProfScope ps(CATRE_K_STN3D, st);
-  if (split) {
-#define LAUNCH_(RS)                                                                                            \
-  hipLaunchKernelGGL(k_stn3d_split<RS>, dim3(tiles * RS), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],     \
-                     prm[CATRE_P_STN_CONV1_B], pkb(packed, L.sp_stn_c2), prm[CATRE_P_STN_CONV2_B],              \
-                     pkb(packed, L.sp_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M)
-    RS_DISPATCH(row_split(tiles), LAUNCH_)
+// The three encoder kernels of one iteration (fp32 or split compute), tile partial maxima -> c.pm.  The probes
+// (catre_*_screen_probe) get CATRE_ERR_UNSUPPORTED where the grid takes no screened form.
+int launch_stn3d(const EncCall& c, const float* const* prm, const float* packed, bool split, unsigned* zero_bar = nullptr,
+                 float* probe_s = nullptr, float* probe_eps = nullptr, float* probe_rows = nullptr) {
+  FormDecision d;
+  if (const int rc = decide(STAGE_STN3D, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
+  const Stn3dW w = stn3d_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));  // conv offsets do not depend on ts_in
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
+  const Stn3dRunArgs run{*c.pts, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, c.pm, w.sc.wps, w.sc.nw, c.B, c.N, c.M, d.S, w.sc.uw};
+  const dim3 grid(d.grid), block(256);
+  ProfScope ps(CATRE_K_STN3D, c.st);
+  switch (d.form) {
+    case CATRE_FORM_SPLIT_RS:
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_stn3d_split<RS>, grid, block, 0, c.st, STN3D_ARGS(c, w))
+      RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
-  } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
-    const int SP = S / 2;
-    const bool f16 = screen_f16_stn_on();
-    hipLaunchKernelGGL(f16 ? k_stn3d_pair_sr16 : k_stn3d_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
-                       Stn3dRunArgs{*pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2),
-                                    prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm,
-                                    pkb(packed, f16 ? L.s16_stn_c3 : L.scr_stn_c3), packed + L.scr_nw_stn, B, N, M, SP,
-                                    packed + L.s16_uw_stn});
-  } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    const bool f16 = screen_f16_stn_on();
-    hipLaunchKernelGGL(f16 ? k_stn3d_pair_sp16 : screen_pool_stn_on() ? k_stn3d_pair_sp : k_stn3d_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
-                       prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M,
-                       ScreenArgs{pkb(packed, f16 ? L.s16_stn_c3 : L.scr_stn_c3), packed + L.scr_nw_stn, probe_s, probe_eps,
-                                  packed + L.s16_uw_stn},
-                       probe_rows);
-  } else if (stn_pair_form(tiles, B, N, M)) {
-    const int pairs = stn_pairs(B, N, M);  // (fewer pairs than CUs: one tile per workgroup keeps the whole chip busy)
-    hipLaunchKernelGGL(k_stn3d_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W], prm[CATRE_P_STN_CONV1_B],
-                       pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B],
-                       ws + W.pm, B, N, M);
-  } else if (row_split8(tiles) == 1 && stn4_on()) {
-    hipLaunchKernelGGL((k_stn3d<1, false, true>), dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
-                       prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, TrainSave{}, zero_bar);
-  } else {
-#define LAUNCH_(RS)                                                                                      \
-  hipLaunchKernelGGL(k_stn3d<RS>, dim3(tiles * RS), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],     \
-                     prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B],           \
-                     pk4(packed, L.stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, TrainSave{}, zero_bar)
-    RS_DISPATCH8(row_split8(tiles), LAUNCH_)
+      break;
+    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_stn3d_pair_sr16, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_RUN: hipLaunchKernelGGL(k_stn3d_pair_sr, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_SCREEN_F16: hipLaunchKernelGGL(k_stn3d_pair_sp16, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN_POOL: hipLaunchKernelGGL(k_stn3d_pair_sp, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN: hipLaunchKernelGGL(k_stn3d_pair_s, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_PAIR: hipLaunchKernelGGL(k_stn3d_pair<false>, grid, block, 0, c.st, STN3D_ARGS(c, w)); break;
+    case CATRE_FORM_WAVE4:
+      hipLaunchKernelGGL((k_stn3d<1, false, true>), grid, block, 0, c.st, STN3D_ARGS(c, w), TrainSave{}, zero_bar);
+      break;
+    default:  // CATRE_FORM_RS8
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_stn3d<RS>, grid, block, 0, c.st, STN3D_ARGS(c, w), TrainSave{}, zero_bar)
+      RS_DISPATCH8(d.row_split, LAUNCH_)
 #undef LAUNCH_
   }
+  return CATRE_OK;
 }
 
-void launch_stnkd(const catre_points* pts, const float* trans3, const float* const* prm, const float* packed, float* ws,
-                  const WsLayout& W, int B, int N, int M, bool split, hipStream_t st, unsigned* zero_bar = nullptr,
-                  float* probe_s = nullptr, float* probe_eps = nullptr, float* probe_rows = nullptr) {
-  const PackLayout L = pack_layout(1);
-  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-  ProfScope ps(CATRE_K_STNKD, st);
-  if (split) {
-#define LAUNCH_(RS)                                                                                                \
-  hipLaunchKernelGGL(k_stnkd_split<RS>, dim3(tiles * RS), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],     \
-                     prm[CATRE_P_CONV1_B], pkb(packed, L.sp_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],                    \
-                     pkb(packed, L.sp_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.sp_fstn_c3),               \
-                     prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M)
-    RS_DISPATCH(row_split(tiles), LAUNCH_)
+int launch_stnkd(const EncCall& c, const float* const* prm, const float* packed, bool split, unsigned* zero_bar = nullptr,
+                 float* probe_s = nullptr, float* probe_eps = nullptr, float* probe_rows = nullptr) {
+  FormDecision d;
+  if (const int rc = decide(STAGE_STNKD, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
+  const StnkdW w = stnkd_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
+  const StnkdRunArgs run{*c.pts, c.trans3, w.wc1, w.bc1, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, c.pm, w.sc.wps, w.sc.nw,
+                         c.B, c.N, c.M, d.S, w.sc.uw};
+  const dim3 grid(d.grid), block(256);
+  ProfScope ps(CATRE_K_STNKD, c.st);
+  switch (d.form) {
+    case CATRE_FORM_SPLIT_RS:
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_stnkd_split<RS>, grid, block, 0, c.st, STNKD_ARGS(c, w))
+      RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
-  } else if (const int S = stn_pair_form(tiles, B, N, M) && screen_run_stn_on() && !probe_s ? screen_run_len(B, N, M) : 1; S > 1) {
-    const int SP = S / 2;
-    const bool f16 = screen_f16_stn_on();
-    hipLaunchKernelGGL(f16 ? k_stnkd_pair_sr16 : k_stnkd_pair_sr, dim3(stn_pair_runs(B, N, M, SP)), dim3(256), 0, st,
-                       StnkdRunArgs{*pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1),
-                                    prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2), prm[CATRE_P_FSTN_CONV2_B],
-                                    pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm,
-                                    pkb(packed, f16 ? L.s16_fstn_c3 : L.scr_fstn_c3), packed + L.scr_nw_fstn, B, N, M, SP,
-                                    packed + L.s16_uw_fstn});
-  } else if (stn_pair_form(tiles, B, N, M) && (screen_stn_on() || probe_s)) {
-    const bool f16 = screen_f16_stn_on();
-    hipLaunchKernelGGL(f16 ? k_stnkd_pair_sp16 : screen_pool_stn_on() ? k_stnkd_pair_sp : k_stnkd_pair_s, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
-                       ScreenArgs{pkb(packed, f16 ? L.s16_fstn_c3 : L.scr_fstn_c3), packed + L.scr_nw_fstn, probe_s, probe_eps,
-                                  packed + L.s16_uw_fstn},
-                       probe_rows);
-  } else if (stn_pair_form(tiles, B, N, M)) {
-    const int pairs = stn_pairs(B, N, M);
-    hipLaunchKernelGGL(k_stnkd_pair<false>, dim3(pairs), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B],
-                       pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2), prm[CATRE_P_FSTN_CONV2_B],
-                       pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
-  } else if (row_split8(tiles) == 1 && stn4_on()) {
-    hipLaunchKernelGGL((k_stnkd<1, false, true>), dim3(tiles), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
-                       TrainSave{}, zero_bar);
-  } else {
-#define LAUNCH_(RS)                                                                                                     \
-  hipLaunchKernelGGL(k_stnkd<RS>, dim3(tiles * RS), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],                \
-                     prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),    \
-                     prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,   \
-                     TrainSave{}, zero_bar)
-    RS_DISPATCH8(row_split8(tiles), LAUNCH_)
+      break;
+    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_stnkd_pair_sr16, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_RUN: hipLaunchKernelGGL(k_stnkd_pair_sr, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_SCREEN_F16: hipLaunchKernelGGL(k_stnkd_pair_sp16, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN_POOL: hipLaunchKernelGGL(k_stnkd_pair_sp, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN: hipLaunchKernelGGL(k_stnkd_pair_s, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_PAIR: hipLaunchKernelGGL(k_stnkd_pair<false>, grid, block, 0, c.st, STNKD_ARGS(c, w)); break;
+    case CATRE_FORM_WAVE4:
+      hipLaunchKernelGGL((k_stnkd<1, false, true>), grid, block, 0, c.st, STNKD_ARGS(c, w), TrainSave{}, zero_bar);
+      break;
+    default:  // CATRE_FORM_RS8
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_stnkd<RS>, grid, block, 0, c.st, STNKD_ARGS(c, w), TrainSave{}, zero_bar)
+      RS_DISPATCH8(d.row_split, LAUNCH_)
 #undef LAUNCH_
   }
+  return CATRE_OK;
 }
 
-void launch_trunk(const catre_points* pts, const float* trans3, const float* trans64, const float* const* prm,
-                  const float* packed, float* pointfeat, float* ws, const WsLayout& W, int B, int N, int M, bool split,
-                  hipStream_t st, float* probe_s = nullptr, float* probe_eps = nullptr) {
-  const PackLayout L = pack_layout(1);
-  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-  ProfScope ps(CATRE_K_TRUNK, st);
-  if (split) {
-#define LAUNCH_(RS)                                                                                           \
-  hipLaunchKernelGGL(k_trunk_split<RS>, dim3(tiles * RS), dim3(512), 0, st, *pts, trans3, trans64,             \
-                     prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B],      \
-                     pkb(packed, L.sp_c3), prm[CATRE_P_CONV3_B], pkb(packed, L.sp_c4), prm[CATRE_P_CONV4_B],   \
-                     ws + W.pm, pointfeat, B, N, M, g_trunk_trace)
-    RS_DISPATCH(row_split(tiles), LAUNCH_)
+int launch_trunk(const EncCall& c, const float* const* prm, const float* packed, float* pointfeat, float* frun, bool split,
+                 float* probe_s = nullptr, float* probe_eps = nullptr) {
+  FormDecision d;
+  if (const int rc = decide(STAGE_TRUNK, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
+  const TrunkW w = trunk_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
+  const TrunkRunArgs run{*c.pts, c.trans3, c.trans64, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, w.w4, w.b4, c.pm, pointfeat,
+                         g_trunk_trace, sc, frun, c.B, c.N, c.M, d.S};
+  const dim3 grid(d.grid);
+  ProfScope ps(CATRE_K_TRUNK, c.st);
+  switch (d.form) {
+    case CATRE_FORM_SPLIT_RS:
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_trunk_split<RS>, grid, dim3(512), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace)
+      RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
-  } else if (const int S = row_split8(tiles) == 1 && trunk4_on() && screen_on() && screen_run_on() ? screen_run_len(B, N, M) : 1;
-             S > 1) {
-    const int runs = B * (((N + TP - 1) / TP + S - 1) / S + ((M + TP - 1) / TP + S - 1) / S);
-    const bool f16 = screen_f16_on();
-    hipLaunchKernelGGL(f16 ? k_trunk4sr16 : k_trunk4sr, dim3(runs), dim3(256), 0, st,
-                       TrunkRunArgs{*pts, trans3, trans64, prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2),
-                                    prm[CATRE_P_CONV2_B], pk4(packed, L.c3), prm[CATRE_P_CONV3_B], pk4(packed, L.c4),
-                                    prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, g_trunk_trace,
-                                    ScreenArgs{pkb(packed, f16 ? L.s16_c4 : L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps,
-                                               packed + L.s16_uw4},
-                                    ws + W.frun, B, N, M, S});
-  } else if (row_split8(tiles) == 1 && trunk4_on() && (screen_on() || probe_s)) {
-    const bool f16 = screen_f16_on();
-    hipLaunchKernelGGL(f16 ? k_trunk4sp16 : screen_pool_on() ? k_trunk4sp : k_trunk4s, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64,
-                       prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
-                       prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                       g_trunk_trace,
-                       ScreenArgs{pkb(packed, f16 ? L.s16_c4 : L.scr_c4), packed + L.scr_nw4, probe_s, probe_eps, packed + L.s16_uw4});
-  } else if (row_split8(tiles) == 1 && trunk4_on()) {
-    hipLaunchKernelGGL(k_trunk4<false>, dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
-                       prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                       g_trunk_trace);
-  } else {
-#define LAUNCH_(RS)                                                                                             \
-  hipLaunchKernelGGL(k_trunk<RS>, dim3(tiles * RS), dim3(512), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W], \
-                     prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),            \
-                     prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M, \
-                     g_trunk_trace)
-    RS_DISPATCH8(row_split8(tiles), LAUNCH_)
+      break;
+    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_trunk4sr16, grid, dim3(256), 0, c.st, run); break;
+    case CATRE_FORM_RUN: hipLaunchKernelGGL(k_trunk4sr, grid, dim3(256), 0, c.st, run); break;
+    case CATRE_FORM_SCREEN_F16:
+      hipLaunchKernelGGL(k_trunk4sp16, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
+      break;
+    case CATRE_FORM_SCREEN_POOL:
+      hipLaunchKernelGGL(k_trunk4sp, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
+      break;
+    case CATRE_FORM_SCREEN: hipLaunchKernelGGL(k_trunk4s, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc); break;
+    case CATRE_FORM_WAVE4: hipLaunchKernelGGL(k_trunk4<false>, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace); break;
+    default:  // CATRE_FORM_RS8
+#define LAUNCH_(RS) hipLaunchKernelGGL(k_trunk<RS>, grid, dim3(512), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace)
+      RS_DISPATCH8(d.row_split, LAUNCH_)
 #undef LAUNCH_
   }
+  return CATRE_OK;
 }
 
 }  // namespace
@@ -2364,7 +2118,7 @@ int catre_stn3d_pool(const catre_points* pts, const float* const* prm, const flo
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  launch_stn3d(pts, prm, packed, ws, W, B, N, M, false, st);
+  if (const int rc = launch_stn3d(EncCall{pts, nullptr, nullptr, ws + W.pm, B, N, M, st}, prm, packed, false)) return rc;
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, pooled, 1024, 1024, B, N, M);
   return check_launch();
 }
@@ -2394,7 +2148,7 @@ int catre_stnkd_pool(const catre_points* pts, const float* trans3, const float* 
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  launch_stnkd(pts, trans3, prm, packed, ws, W, B, N, M, false, st);
+  if (const int rc = launch_stnkd(EncCall{pts, trans3, nullptr, ws + W.pm, B, N, M, st}, prm, packed, false)) return rc;
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, pooled, 1024, 1024, B, N, M);
   return check_launch();
 }
@@ -2407,7 +2161,8 @@ int catre_trunk(const catre_points* pts, const float* trans3, const float* trans
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st);
+  if (const int rc = launch_trunk(EncCall{pts, trans3, trans64, ws + W.pm, B, N, M, st}, prm, packed, pointfeat, ws + W.frun, false))
+    return rc;
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
   return check_launch();
 }
@@ -2450,11 +2205,10 @@ int catre_trunk_w(const catre_points* pts, const float* trans3, const float* tra
   hipStream_t st = (hipStream_t)stream;
   const PackLayout L = pack_layout(1);
   const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-#define LAUNCH_(MB, NB)                                                                                                \
-  hipLaunchKernelGGL((k_trunkw<MB, NB>), dim3(tiles), dim3(512), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],   \
-                     prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),                 \
-                     prm[CATRE_P_CONV3_B], pk4(packed, L.total), prm[CATRE_P_CONV4_B], out_dim / 32, ws + W.pm,        \
-                     pointfeat, B, N, M)
+  const TrunkW w = trunk_weights(prm, packed, L, PK_F32);  // conv4: the out_dim rows behind the layout
+#define LAUNCH_(MB, NB)                                                                                                   \
+  hipLaunchKernelGGL((k_trunkw<MB, NB>), dim3(tiles), dim3(512), 0, st, *pts, trans3, trans64, w.w1, w.b1, w.w2, w.b2, w.w3, \
+                     w.b3, pk4(packed, L.total), w.b4, out_dim / 32, ws + W.pm, pointfeat, B, N, M)
   switch (out_dim) {
     case 1024: LAUNCH_(4, 2); break;
     case 512: LAUNCH_(2, 2); break;
@@ -2473,11 +2227,12 @@ int catre_trunk_screen_probe(const catre_points* pts, const float* trans3, const
   REQUIRE(pts && trans3 && prm && packed && screen && eps && gfeat && pointfeat && workspace && dims_ok1(B, N, M));
   const WsLayout W = ws_layout(B, N, M);
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
-  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-  if (row_split8(tiles) != 1 || !trunk4_on()) return CATRE_ERR_UNSUPPORTED;  // the screened form exists for full grids only
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  launch_trunk(pts, trans3, trans64, prm, packed, pointfeat, ws, W, B, N, M, false, st, screen, eps);
+  // (CATRE_ERR_UNSUPPORTED: the screened form exists for full grids only)
+  if (const int rc = launch_trunk(EncCall{pts, trans3, trans64, ws + W.pm, B, N, M, st}, prm, packed, pointfeat, ws + W.frun, false,
+                                  screen, eps))
+    return rc;
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, gfeat, PMW, PMW, B, N, M);
   return check_launch();
 }
@@ -2489,14 +2244,13 @@ int catre_stn_screen_probe(int which, const catre_points* pts, const float* tran
           workspace && dims_ok1(B, N, M));
   const WsLayout W = ws_layout(B, N, M);
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
-  const int tiles = B * ((N + TP - 1) / TP + (M + TP - 1) / TP);
-  if (!stn_pair_form(tiles, B, N, M)) return CATRE_ERR_UNSUPPORTED;  // the screened form exists for the full-grid pair kernels only
   float* ws = (float*)workspace;
   hipStream_t st = (hipStream_t)stream;
-  if (which == 0)
-    launch_stn3d(pts, prm, packed, ws, W, B, N, M, false, st, nullptr, screen, eps, rows);
-  else
-    launch_stnkd(pts, trans3, prm, packed, ws, W, B, N, M, false, st, nullptr, screen, eps, rows);
+  const EncCall c{pts, trans3, nullptr, ws + W.pm, B, N, M, st};
+  // (CATRE_ERR_UNSUPPORTED: the screened form exists for the full-grid pair kernels only)
+  if (const int rc = which == 0 ? launch_stn3d(c, prm, packed, false, nullptr, screen, eps, rows)
+                                : launch_stnkd(c, prm, packed, false, nullptr, screen, eps, rows))
+    return rc;
   hipLaunchKernelGGL(k_reduce_pm, dim3(n_clouds(B, M), (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, pooled, 1024, 1024, B, N, M);
   return check_launch();
 }
@@ -2555,7 +2309,7 @@ static int rot_head_impl(const float* gfeat, const float* pointfeat, const float
                          pkb(packed, L.sp_rot_l0[1]), ws + W.aff0, pkb(packed, L.sp_rot_l1[0]), pkb(packed, L.sp_rot_l1[1]),
                          prm[CATRE_P_ROTX_L1_B], prm[CATRE_P_ROTY_L1_B], ws + W.y1, ws + W.gn1, B, N, M,
                          g_trunk_trace ? g_trunk_trace + ((size_t)1 << 24) : nullptr);
-    else if (B * T >= ROTW_MIN_TILES && rotw_on()) {
+    else if (B * T >= ROTW_MIN_TILES && form_on(SW_ROTW)) {
       // grids that fill the chip: one wave per SIMD, a tile per wave (same bits as k_rot_l1)
       hipLaunchKernelGGL(k_rot_l1w, dim3((B * T + 3) / 4), dim3(256), 0, st, pointfeat, pk4(packed, L.rot_l0[0]),
                          pk4(packed, L.rot_l0[1]), ws + W.aff0, pk4(packed, L.rot_l1[0]), pk4(packed, L.rot_l1[1]),
@@ -2656,42 +2410,37 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
                           int N, int M, hipStream_t st, float* pose_echo, float* scale_echo) {
   const PackLayout L = pack_layout(1);
   // the operand pack of a layer: its bf16 or its fp16 image
+  constexpr PackKind PK = is_f16_op<OT>() ? PK_F16 : PK_BF16;
   auto pk = [&](size_t bf, size_t hf) { return pkb(packed, is_f16_op<OT>() ? hf : bf); };
-  const int TN = (N + TP - 1) / TP, TM = (M + TP - 1) / TP, T = TN + TM, tiles = B * T;
+  const int T = (N + TP - 1) / TP + (M + TP - 1) / TP;
   const int rd = catre_rot_dim(o->rot_type) / 2;
   int rc;
-  // grids that fill the chip twice over take PAIRS of tiles per workgroup in all three encoder kernels (same bits, fewer
-  // prologues and weight fetches per MFMA); below that the 64-point kernels spread better
-  const int pairs = B * ((TN + 1) / 2 + (TM + 1) / 2);
-  const bool paired = pairs >= bf_pair_min();
+  // all three encoder kernels take the same form (pairs of tiles or single tiles: catre_forms.h) and so the same grid
+  FormDecision d;
+  if ((rc = decide(STAGE_STN3D, MODE_BF16, false, false, false, B, N, M, &d))) return rc;
+  const bool paired = d.form == CATRE_FORM_BF_PAIR;
+  EncCall c{pts, nullptr, nullptr, ws + W.pm, B, N, M, st};
   {
+    const Stn3dW w = stn3d_weights(prm, packed, L, PK);
     ProfScope ps(CATRE_K_STN3D, st);
     if (paired)
-      LP_LAUNCH((k_stn3d_bf2<false>), k_stn3d_hf2, dim3(pairs), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                prm[CATRE_P_STN_CONV1_B], pk(L.bf_stn_c2, L.f16_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                pk(L.bf_stn_c3, L.f16_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
+      LP_LAUNCH((k_stn3d_bf2<false>), k_stn3d_hf2, dim3(d.grid), dim3(256), 0, st, STN3D_ARGS(c, w));
     else
-      LP_LAUNCH((k_stn3d_bf<false>), k_stn3d_hf, dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                prm[CATRE_P_STN_CONV1_B], pk(L.bf_stn_c2, L.f16_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                pk(L.bf_stn_c3, L.f16_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M);
+      LP_LAUNCH((k_stn3d_bf<false>), k_stn3d_hf, dim3(d.grid), dim3(256), 0, st, STN3D_ARGS(c, w));
   }
+  c.trans3 = ws + W.trans3;
   hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.pool, 1024, 1024, B, N, M);
   if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_STN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans3, 3, 2 * B, st)))
     return rc;
   const float* t64 = nullptr;
   if (o->feature_transform) {
     {
+      const StnkdW w = stnkd_weights(prm, packed, L, PK);
       ProfScope ps(CATRE_K_STNKD, st);
       if (paired)
-        LP_LAUNCH((k_stnkd_bf2<false>), k_stnkd_hf2, dim3(pairs), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
-                  prm[CATRE_P_CONV1_B], pk(L.bf_fstn_c1, L.f16_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
-                  pk(L.bf_fstn_c2, L.f16_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pk(L.bf_fstn_c3, L.f16_fstn_c3),
-                  prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
+        LP_LAUNCH((k_stnkd_bf2<false>), k_stnkd_hf2, dim3(d.grid), dim3(256), 0, st, STNKD_ARGS(c, w));
       else
-        LP_LAUNCH((k_stnkd_bf<false>), k_stnkd_hf, dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, prm[CATRE_P_CONV1_W],
-                  prm[CATRE_P_CONV1_B], pk(L.bf_fstn_c1, L.f16_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
-                  pk(L.bf_fstn_c2, L.f16_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pk(L.bf_fstn_c3, L.f16_fstn_c3),
-                  prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M);
+        LP_LAUNCH((k_stnkd_bf<false>), k_stnkd_hf, dim3(d.grid), dim3(256), 0, st, STNKD_ARGS(c, w));
     }
     hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (1024 + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.pool, 1024, 1024, B, N, M);
     if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_FSTN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans64, 64, 2 * B, st)))
@@ -2700,17 +2449,13 @@ static int refine_iter_bf(const catre_points* pts, const float* init_pose, const
   }
   u32x4* pointfeat = reinterpret_cast<u32x4*>(ws + W.pointfeat);
   {
+    c.trans64 = t64;
+    const TrunkW w = trunk_weights(prm, packed, L, PK);
     ProfScope ps(CATRE_K_TRUNK, st);
     if (paired)
-      LP_LAUNCH((k_trunk_bf2<false>), k_trunk_hf2, dim3(pairs), dim3(512), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
-                prm[CATRE_P_CONV1_B], pk(L.bf_c2, L.f16_c2), prm[CATRE_P_CONV2_B], pk(L.bf_c3, L.f16_c3),
-                prm[CATRE_P_CONV3_B], pk(L.bf_c4, L.f16_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                g_trunk_trace);
+      LP_LAUNCH((k_trunk_bf2<false>), k_trunk_hf2, dim3(d.grid), dim3(512), 0, st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace);
     else
-      LP_LAUNCH(k_trunk_bf, k_trunk_hf, dim3(tiles), dim3(256), 0, st, *pts, ws + W.trans3, t64, prm[CATRE_P_CONV1_W],
-                prm[CATRE_P_CONV1_B], pk(L.bf_c2, L.f16_c2), prm[CATRE_P_CONV2_B], pk(L.bf_c3, L.f16_c3),
-                prm[CATRE_P_CONV3_B], pk(L.bf_c4, L.f16_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pointfeat, B, N, M,
-                g_trunk_trace);
+      LP_LAUNCH(k_trunk_bf, k_trunk_hf, dim3(d.grid), dim3(256), 0, st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace);
   }
   hipLaunchKernelGGL(k_reduce_pm, dim3(2 * B, (PMW + 255) / 256), dim3(256), 0, st, ws + W.pm, ws + W.gfeat, PMW, PMW, B, N, M);
   if ((rc = catre_ts_head(ws + W.gfeat, init_pose, init_scale, prm, packed, o, ws + W.dt, ws + W.ds, ws,
@@ -2797,35 +2542,35 @@ static int refine_iter_impl(const catre_points* pts, const float* init_pose, con
   };
   // STN3d (pointnet.py:98) on both clouds
   // small fp32 batches: each FC tail as ONE launch (k_fc_tail); its barrier counters are zeroed by the encoder kernel in front
-  unsigned* bar = small && !split && fc_tail_on() ? reinterpret_cast<unsigned*>(ws + W.bar) : nullptr;
-  launch_stn3d(pts, prm, packed, ws, W, B, N, M, split, st, bar);
+  unsigned* bar = small && !split && form_on(SW_FC_TAIL) ? reinterpret_cast<unsigned*>(ws + W.bar) : nullptr;
+  EncCall c{pts, nullptr, nullptr, ws + W.pm, B, N, M, st};
+  if ((rc = launch_stn3d(c, prm, packed, split, bar))) return rc;
+  c.trans3 = ws + W.trans3;
   if (!fold) reduce_pm(ws + W.pool, 1024, 1024);
   if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_STN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans3, 3, R, st, pm, B, N, M,
                         bar)))
     return rc;
   const float* t64 = nullptr;
   if (o->feature_transform) {  // STNkd (pointnet.py:105-106)
-    launch_stnkd(pts, ws + W.trans3, prm, packed, ws, W, B, N, M, split, st, bar);
+    if ((rc = launch_stnkd(c, prm, packed, split, bar))) return rc;
     if (!fold) reduce_pm(ws + W.pool, 1024, 1024);
     if ((rc = stn_fc_tail(ws + W.pool, prm, CATRE_P_FSTN_FC1_W, ws + W.h1, ws + W.h2, ws + W.trans64, 64, R, st, pm, B, N,
                           M, bar)))
       return rc;
     t64 = ws + W.trans64;
   }
+  c.trans64 = t64;
   // a handful of objects, fp32: the trunk on HALF tiles (32 points per workgroup: half the per-tile prologue)
   const int rsh = small && !split ? trunk_h_split(B * T) : 0;
   if (rsh) {
-    const PackLayout L = pack_layout(1);
+    const TrunkW w = trunk_weights(prm, packed, pack_layout(1), PK_F32);
     ProfScope ps(CATRE_K_TRUNK, st);
-#define LAUNCH_(RSH)                                                                                                  \
-  hipLaunchKernelGGL(k_trunk_h<RSH>, dim3(B * T * 2 * RSH), dim3(512), 0, st, *pts, (const float*)(ws + W.trans3), t64,  \
-                     prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B],               \
-                     pk4(packed, L.c3), prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm,       \
-                     ws + W.pointfeat, B, N, M)
+#define LAUNCH_(RSH) \
+  hipLaunchKernelGGL(k_trunk_h<RSH>, dim3(B * T * 2 * RSH), dim3(512), 0, st, TRUNK_ARGS(c, w, ws + W.pointfeat))
     RS_DISPATCH(rsh, LAUNCH_)
 #undef LAUNCH_
-  } else {
-    launch_trunk(pts, ws + W.trans3, t64, prm, packed, ws + W.pointfeat, ws, W, B, N, M, split, st);
+  } else if ((rc = launch_trunk(c, prm, packed, ws + W.pointfeat, ws + W.frun, split))) {
+    return rc;
   }
   if (!small) {
     reduce_pm(ws + W.gfeat, PMW, PMW);
@@ -3016,8 +2761,8 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
-  if (id < 0 || id > 9) return -1;
-  const int bit = 1 << id;
+  if (id < 0 || id >= SW_PUBLIC) return -1;
+  const int bit = sw(id);
   const int cur = forms();
   if (value >= 0) g_forms.store(value ? (cur | bit) : (cur & ~bit), std::memory_order_relaxed);
   return (cur & bit) ? 1 : 0;
@@ -3032,6 +2777,16 @@ int catre_screen_run_len(int value) {
 int catre_screen_run_rule(int B, int N, int M, int cus) {
   if (B <= 0 || N <= 0 || M < 0 || cus <= 0) return -1;
   return screen_run_rule(B, N, M, cus);
+}
+
+int catre_form_decision(int stage, int mode, int save, int rows, int probe, int B, int N, int M, int switches, int cus,
+                        int run_len, int bf_pair_min, int* out) {
+  FormDecision d;
+  if (!out || !form_decision(stage, mode, save != 0, rows != 0, probe != 0, B, N, M, switches < 0 ? -1 : effective_forms(switches), cus,
+                             run_len, bf_pair_min, &d))
+    return -1;
+  out[0] = d.form, out[1] = d.row_split, out[2] = d.S, out[3] = d.grid;
+  return 0;
 }
 
 int catre_debug_knob(int id, int value) {

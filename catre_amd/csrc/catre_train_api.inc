@@ -1470,7 +1470,13 @@ int catre_op_optim_step(int kind, const void* tensors, int n_tensors, const void
 // block computes the pooled feature AND writes the activations the layer-wise backward reads (cloud-major point rows),
 // instead of one row GEMM per layer with every intermediate streamed through HBM twice.  N, M multiples of 64.
 namespace {
-inline int bf_pairs(int B, int N, int M) { return B * (((N + TP - 1) / TP + 1) / 2 + ((M + TP - 1) / TP + 1) / 2); }
+// the compute mode and the weight images of a training forward
+inline int train_mode(int compute_dtype) {
+  return compute_dtype == CATRE_DTYPE_BF16 ? MODE_BF16 : compute_dtype == CATRE_DTYPE_SPLIT ? MODE_SPLIT : MODE_F32;
+}
+inline PackKind train_pack(int compute_dtype) {
+  return compute_dtype == CATRE_DTYPE_BF16 ? PK_BF16 : compute_dtype == CATRE_DTYPE_SPLIT ? PK_SPLIT : PK_F32;
+}
 inline bool train_dims_ok(int B, int N, int M) { return B > 0 && N > 0 && M > 0 && N % TP == 0 && M % TP == 0; }
 struct TrainScratch {
   float* pmax;
@@ -1492,34 +1498,22 @@ int catre_train_stn3d_fwd(const catre_points* pts, const float* const* prm, cons
   const WsLayout W = ws_layout(B, N, M);
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
-  const PackLayout L = pack_layout(1);
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = B * (N + M) / TP;
-  const TrainScratch sc = train_scratch(ws, W, tiles);
+  const TrainScratch sc = train_scratch(ws, W, B * (N + M) / TP);
   TrainSave sv{a1, a2, nullptr, nullptr, nullptr, sc.pmax, sc.pidx};
-  if (compute_dtype == CATRE_DTYPE_BF16 && bf_pairs(B, N, M) >= bf_pair_min())
+  FormDecision d;
+  if (const int rc = decide(STAGE_STN3D, train_mode(compute_dtype), true, a1 != nullptr, false, B, N, M, &d)) return rc;
+  const EncCall c{pts, nullptr, nullptr, ws + W.pm, B, N, M, st};
+  const Stn3dW w = stn3d_weights(prm, packed, pack_layout(1), train_pack(compute_dtype));
+  const dim3 grid(d.grid), block(256);
+  switch (d.form) {
     // grids that fill the chip: the 128-point pair kernel of the inference path with saves (221 -> ~140 us at B = 256)
-    hipLaunchKernelGGL((k_stn3d_bf2<true>), dim3(bf_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pkb(packed, L.bf_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                       pkb(packed, L.bf_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else if (compute_dtype == CATRE_DTYPE_BF16)
-    hipLaunchKernelGGL((k_stn3d_bf<true>), dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pkb(packed, L.bf_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                       pkb(packed, L.bf_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else if (compute_dtype == CATRE_DTYPE_SPLIT)
-    hipLaunchKernelGGL((k_stn3d_split<1, true>), dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pkb(packed, L.sp_stn_c2), prm[CATRE_P_STN_CONV2_B],
-                       pkb(packed, L.sp_stn_c3), prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else if (!a1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256)
-    // no activation rows asked for (the backward recomputes them on its live rows): the inference pair kernel with the
-    // arg-max epilogue
-    hipLaunchKernelGGL(k_stn3d_pair<true>, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
-                       prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else  // (the one-wave-per-SIMD form does not pay WITH saves: 470 MB of activation saves per launch want a second resident workgroup)
-    hipLaunchKernelGGL((k_stn3d<1, true>), dim3(tiles), dim3(256), 0, st, *pts, prm[CATRE_P_STN_CONV1_W],
-                       prm[CATRE_P_STN_CONV1_B], pk4(packed, L.stn_c2), prm[CATRE_P_STN_CONV2_B], pk4(packed, L.stn_c3),
-                       prm[CATRE_P_STN_CONV3_B], ws + W.pm, B, N, M, sv);
+    case CATRE_FORM_TRAIN_BF_PAIR: hipLaunchKernelGGL((k_stn3d_bf2<true>), grid, block, 0, st, STN3D_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_BF: hipLaunchKernelGGL((k_stn3d_bf<true>), grid, block, 0, st, STN3D_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_SPLIT: hipLaunchKernelGGL((k_stn3d_split<1, true>), grid, block, 0, st, STN3D_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_PAIR: hipLaunchKernelGGL(k_stn3d_pair<true>, grid, block, 0, st, STN3D_ARGS(c, w), sv); break;
+    default: hipLaunchKernelGGL((k_stn3d<1, true>), grid, block, 0, st, STN3D_ARGS(c, w), sv);  // CATRE_FORM_TRAIN_RS1
+  }
   hipLaunchKernelGGL(k_maxpool_tiles, dim3(2 * B, 4), dim3(256), 0, st, (const float*)sc.pmax, (const int*)sc.pidx, g, idx,
                      1024, B, N, M);
   return check_launch();
@@ -1535,34 +1529,21 @@ int catre_train_stnkd_fwd(const catre_points* pts, const float* trans3, const fl
   const WsLayout W = ws_layout(B, N, M);
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
-  const PackLayout L = pack_layout(1);
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = B * (N + M) / TP;
-  const TrainScratch sc = train_scratch(ws, W, tiles);
+  const TrainScratch sc = train_scratch(ws, W, B * (N + M) / TP);
   TrainSave sv{f1, f2, nullptr, nullptr, nullptr, sc.pmax, sc.pidx};
-  if (compute_dtype == CATRE_DTYPE_BF16 && bf_pairs(B, N, M) >= bf_pair_min())
-    hipLaunchKernelGGL((k_stnkd_bf2<true>), dim3(bf_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pkb(packed, L.bf_fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pkb(packed, L.bf_fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.bf_fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
-                       sv);
-  else if (compute_dtype == CATRE_DTYPE_BF16)
-    hipLaunchKernelGGL((k_stnkd_bf<true>), dim3(tiles), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pkb(packed, L.bf_fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pkb(packed, L.bf_fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.bf_fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M,
-                       sv);
-  else if (compute_dtype == CATRE_DTYPE_SPLIT)
-    hipLaunchKernelGGL((k_stnkd_split<1, true>), dim3(tiles), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pkb(packed, L.sp_fstn_c1), prm[CATRE_P_FSTN_CONV1_B],
-                       pkb(packed, L.sp_fstn_c2), prm[CATRE_P_FSTN_CONV2_B], pkb(packed, L.sp_fstn_c3),
-                       prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else if (!f1 && stn4_on() && stn_pair_on() && stn_pairs(B, N, M) >= 256)
-    hipLaunchKernelGGL(k_stnkd_pair<true>, dim3(stn_pairs(B, N, M)), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M, sv);
-  else
-    hipLaunchKernelGGL((k_stnkd<1, true>), dim3(tiles), dim3(256), 0, st, *pts, trans3, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.fstn_c1), prm[CATRE_P_FSTN_CONV1_B], pk4(packed, L.fstn_c2),
-                       prm[CATRE_P_FSTN_CONV2_B], pk4(packed, L.fstn_c3), prm[CATRE_P_FSTN_CONV3_B], ws + W.pm, B, N, M, sv);
+  FormDecision d;
+  if (const int rc = decide(STAGE_STNKD, train_mode(compute_dtype), true, f1 != nullptr, false, B, N, M, &d)) return rc;
+  const EncCall c{pts, trans3, nullptr, ws + W.pm, B, N, M, st};
+  const StnkdW w = stnkd_weights(prm, packed, pack_layout(1), train_pack(compute_dtype));
+  const dim3 grid(d.grid), block(256);
+  switch (d.form) {
+    case CATRE_FORM_TRAIN_BF_PAIR: hipLaunchKernelGGL((k_stnkd_bf2<true>), grid, block, 0, st, STNKD_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_BF: hipLaunchKernelGGL((k_stnkd_bf<true>), grid, block, 0, st, STNKD_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_SPLIT: hipLaunchKernelGGL((k_stnkd_split<1, true>), grid, block, 0, st, STNKD_ARGS(c, w), sv); break;
+    case CATRE_FORM_TRAIN_PAIR: hipLaunchKernelGGL(k_stnkd_pair<true>, grid, block, 0, st, STNKD_ARGS(c, w), sv); break;
+    default: hipLaunchKernelGGL((k_stnkd<1, true>), grid, block, 0, st, STNKD_ARGS(c, w), sv);  // CATRE_FORM_TRAIN_RS1
+  }
   hipLaunchKernelGGL(k_maxpool_tiles, dim3(2 * B, 4), dim3(256), 0, st, (const float*)sc.pmax, (const int*)sc.pidx, g, idx,
                      1024, B, N, M);
   return check_launch();
@@ -1579,34 +1560,24 @@ int catre_train_trunk_fwd(const catre_points* pts, const float* trans3, const fl
   const WsLayout W = ws_layout(B, N, M);
   if (ws_bytes < W.total * sizeof(float)) return CATRE_ERR_WORKSPACE;
   float* ws = (float*)workspace;
-  const PackLayout L = pack_layout(1);
   hipStream_t st = (hipStream_t)stream;
-  const int tiles = B * (N + M) / TP;
-  const TrainScratch sc = train_scratch(ws, W, tiles);
+  const TrainScratch sc = train_scratch(ws, W, B * (N + M) / TP);
   TrainSave sv{x1, h1, a2, a3, pf, sc.pmax, sc.pidx};
-  if (compute_dtype == CATRE_DTYPE_BF16) {
-    const int TN = N / TP, TM = M / TP, pairs = B * ((TN + 1) / 2 + (TM + 1) / 2);
-    hipLaunchKernelGGL((k_trunk_bf2<true>), dim3(pairs), dim3(512), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pkb(packed, L.bf_c2), prm[CATRE_P_CONV2_B], pkb(packed, L.bf_c3),
-                       prm[CATRE_P_CONV3_B], pkb(packed, L.bf_c4), prm[CATRE_P_CONV4_B], ws + W.pm, (u32x4*)nullptr, B, N, M,
-                       (unsigned long long*)nullptr, sv);
-  } else if (compute_dtype == CATRE_DTYPE_SPLIT) {
-    hipLaunchKernelGGL((k_trunk_split<1, true>), dim3(tiles), dim3(512), 0, st, *pts, trans3, trans64,
-                       prm[CATRE_P_CONV1_W], prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B],
-                       pkb(packed, L.sp_c3), prm[CATRE_P_CONV3_B], pkb(packed, L.sp_c4), prm[CATRE_P_CONV4_B], ws + W.pm, pf, B,
-                       N, M, (unsigned long long*)nullptr, sv);
-  } else if (trunk4_on() && row_split8(tiles) == 1) {
-    // (gated like the inference launch: k_trunk4 is the form for grids that fill the chip - one wave per SIMD; fewer tiles
-    // than workgroup slots keep the 8-wave kernel.  Same bits either way.)
-    hipLaunchKernelGGL((k_trunk4<true>), dim3(tiles), dim3(256), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
-                       prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pf, B, N, M,
-                       (unsigned long long*)nullptr, sv);
-  } else {
-    hipLaunchKernelGGL((k_trunk<1, true>), dim3(tiles), dim3(512), 0, st, *pts, trans3, trans64, prm[CATRE_P_CONV1_W],
-                       prm[CATRE_P_CONV1_B], pk4(packed, L.c2), prm[CATRE_P_CONV2_B], pk4(packed, L.c3),
-                       prm[CATRE_P_CONV3_B], pk4(packed, L.c4), prm[CATRE_P_CONV4_B], ws + W.pm, pf, B, N, M,
-                       (unsigned long long*)nullptr, sv);
+  FormDecision d;
+  if (const int rc = decide(STAGE_TRUNK, train_mode(compute_dtype), true, true, false, B, N, M, &d)) return rc;
+  const EncCall c{pts, trans3, trans64, ws + W.pm, B, N, M, st};
+  const TrunkW w = trunk_weights(prm, packed, pack_layout(1), train_pack(compute_dtype));
+  const dim3 grid(d.grid);
+  unsigned long long* const no_trace = nullptr;
+  switch (d.form) {
+    case CATRE_FORM_TRAIN_BF_PAIR:
+      hipLaunchKernelGGL((k_trunk_bf2<true>), grid, dim3(512), 0, st, TRUNK_ARGS(c, w, (u32x4*)nullptr), no_trace, sv);
+      break;
+    case CATRE_FORM_TRAIN_SPLIT: hipLaunchKernelGGL((k_trunk_split<1, true>), grid, dim3(512), 0, st, TRUNK_ARGS(c, w, pf), no_trace, sv); break;
+    // k_trunk4 is the form for grids that fill the chip - one wave per SIMD; fewer tiles than workgroup slots keep the
+    // 8-wave kernel.  Same bits either way.
+    case CATRE_FORM_TRAIN_WAVE4: hipLaunchKernelGGL((k_trunk4<true>), grid, dim3(256), 0, st, TRUNK_ARGS(c, w, pf), no_trace, sv); break;
+    default: hipLaunchKernelGGL((k_trunk<1, true>), grid, dim3(512), 0, st, TRUNK_ARGS(c, w, pf), no_trace, sv);  // CATRE_FORM_TRAIN_RS1
   }
   hipLaunchKernelGGL(k_maxpool_tiles, dim3(2 * B, 4), dim3(256), 0, st, (const float*)sc.pmax, (const int*)sc.pidx, g, idx,
                      1024, B, N, M);

@@ -148,6 +148,7 @@ _SIGS = {
     "catre_form_switch": (_I, [_I, _I]),
     "catre_screen_run_len": (_I, [_I]),
     "catre_screen_run_rule": (_I, [_I, _I, _I, _I]),
+    "catre_form_decision": (_I, [_I] * 12 + [ctypes.POINTER(ctypes.c_int)]),
     "catre_refine_k_from": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _SZ, _I, _I, _I, _I, _P]),
     "catre_colmax": (_I, [_P, _P, _I, _I, _I, _P]),
     # training ops (include/catre_hip.h "training ops")
@@ -306,6 +307,26 @@ def screen_run_len(value=None):
 def screen_run_rule(B, N, M, cus=256):
     """The run length the library's rule picks for a (B, N, M) grid on `cus` compute units (a pure host function)."""
     return load().catre_screen_run_rule(B, N, M, cus)
+
+
+# catre_kernel_form, in the order the launches try them
+KERNEL_FORMS = ("unsupported", "split_rs", "run_f16", "run", "screen_f16", "screen_pool", "screen", "pair", "wave4", "rs8",
+                "bf_pair", "bf", "train_split", "train_pair", "train_wave4", "train_rs1", "train_bf_pair", "train_bf")
+# bits of `switches`: ``FORM_IDS`` and the STN arms, which follow the environment only (CATRE_SCREEN_POOL_STN / _RUN_STN / _F16_STN)
+SWITCH_BITS = dict(FORM_IDS, screen_pool_stn=10, screen_run_stn=11, screen_f16_stn=12)
+STAGES = {"stn3d": 0, "stnkd": 1, "trunk": 2}
+MODES = {"fp32": 0, "split": 1, "bf16": 2}
+
+
+def form_decision(stage, mode, B, N, M, switches, save=False, rows=False, probe=False, cus=256, run_len=0, bf_pair_min=512):
+    """The kernel form one launch of `stage` (``STAGES``) in `mode` (``MODES``) takes under the switch word `switches`
+    (``SWITCH_BITS``): (form name of ``KERNEL_FORMS``, workgroups per tile, tiles - STN stages: pairs - per run, grid).
+    A pure host function of the library, the one its launches call; None for arguments no caller can produce."""
+    out = (ctypes.c_int * 4)()
+    if load().catre_form_decision(STAGES[stage], MODES[mode], int(save), int(rows), int(probe), B, N, M, switches, cus, run_len,
+                                  bf_pair_min, out):
+        return None
+    return KERNEL_FORMS[out[0]], out[1], out[2], out[3]
 
 
 def capture_id(device):

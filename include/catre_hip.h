@@ -367,6 +367,26 @@ int catre_screen_run_len(int value);
  * each up to S tiles long, takes no more tile slots on `cus` compute units (one workgroup per unit) than the one-tile
  * grid - ceil(runs / cus) S <= ceil(tiles / cus) - else 1.  TN, TM: 64-point tiles of a cloud.  -1 for bad arguments. */
 int catre_screen_run_rule(int B, int N, int M, int cus);
+/* The kernel form one launch of an encoder stage takes - every branch the launches have, in the order they are tried:
+ * fp32 / split inference (SPLIT_RS: the split kernels on 1 / 2 / 4 workgroups per tile; RUN_F16 .. SCREEN: the screened
+ * max-pool of switches 5 - 9 on the wide kernels; PAIR: the STN kernels on pairs of tiles; WAVE4: one wave per SIMD;
+ * RS8: the 8-wave kernels on 1 .. 8 workgroups per tile), the bf16 / fp16-operand kernels on pairs of tiles or on single
+ * tiles, and the training forwards (with saves).  UNSUPPORTED: a probe on a grid that takes no screened form. */
+typedef enum catre_kernel_form {
+  CATRE_FORM_UNSUPPORTED = 0, CATRE_FORM_SPLIT_RS, CATRE_FORM_RUN_F16, CATRE_FORM_RUN, CATRE_FORM_SCREEN_F16,
+  CATRE_FORM_SCREEN_POOL, CATRE_FORM_SCREEN, CATRE_FORM_PAIR, CATRE_FORM_WAVE4, CATRE_FORM_RS8, CATRE_FORM_BF_PAIR,
+  CATRE_FORM_BF, CATRE_FORM_TRAIN_SPLIT, CATRE_FORM_TRAIN_PAIR, CATRE_FORM_TRAIN_WAVE4, CATRE_FORM_TRAIN_RS1,
+  CATRE_FORM_TRAIN_BF_PAIR, CATRE_FORM_TRAIN_BF
+} catre_kernel_form;
+/* The form decision, a pure host function (the launches call it with the process's switches, the device's CU count,
+ * catre_screen_run_len and CATRE_BF_PAIR_MIN).  stage 0 STN3d / 1 STNkd / 2 trunk; mode 0 fp32 / 1 split / 2 bf16 (and fp16
+ * operands); save: a training forward, rows: it writes the activation rows; probe: a catre_*_screen_probe call; switches:
+ * bit id of catre_form_switch, bits 10 - 12 the STN arms CATRE_SCREEN_POOL_STN / _RUN_STN / _F16_STN - a switch counts as off
+ * while one it refines is off; run_len 0 .. 16 (0: catre_screen_run_rule on `cus`).  Writes out[0] the catre_kernel_form,
+ * out[1] workgroups per tile, out[2] tiles per run (STN stages: pairs per run; 1 outside the run forms), out[3] the grid
+ * in workgroups and returns 0; -1 for arguments no caller can produce. */
+int catre_form_decision(int stage, int mode, int save, int rows, int probe, int B, int N, int M, int switches, int cus,
+                        int run_len, int bf_pair_min, int* out);
 /* Experiment knobs of the instrumented library (id 0: start offset in cycles between the co-resident workgroups of the
  * STN kernels' first dispatch round, id 2: the screened kernels' counters of catre_debug_screen_counts on (1, default) / off
  * (0) - their atomics distort the phase stamps); CATRE_ERR_UNSUPPORTED in the product library. */
