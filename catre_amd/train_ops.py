@@ -15,6 +15,7 @@ import torch
 import torch.nn.functional as F
 
 from . import hip
+from . import train_route as TR
 
 logger = logging.getLogger(__name__)
 _scratch = {}
@@ -173,11 +174,12 @@ def _pack_split(w, J, K, dev, transpose=0):
     return wp
 
 
-def _tiled_gemm_ok(R, J, K, min_rows=2048):
-    """Shapes the tiled row kernel (catre_op_gemm_rows) takes."""
-    # (64-row tiles: under ~2048 rows - the FC tails, whose rows are clouds - the tiled kernel would put a handful of
-    # workgroups on 256 CUs; the split-K catre_linear takes those)
-    return (J % 32 == 0) and (J <= 256 or J in (512, 1024)) and (K in (8, 16, 32, 64, 128) or K % 256 == 0) and R >= min_rows
+_tiled_gemm_ok = TR.tiled_gemm_ok
+
+
+def _jk(w):
+    """A weight's (rows, columns), trailing dimensions folded into the columns - what the predicates of train_route read."""
+    return w.shape[0], w.numel() // max(w.shape[0], 1)
 
 
 def _gemm_nt(x, w, bias, relu, mask=None, identity_k=0, xmask=None, amp=False, wT=None):
@@ -637,7 +639,8 @@ def _dgrad_n(dy, w2, xmask, count, amp=0, mask=None, mask_rows=None):
         assert mask.shape[1] == K
         # (bf16 rows: what the autocast encoder forward saves - only the bf16-operand kernel reads them)
         rows_bf16 = hip.ROWS_BF16 if mask.dtype == torch.bfloat16 else 0
-        assert not rows_bf16 or amp == 1, "bf16 activation rows are read by the bf16-operand row GEMMs only"
+        if rows_bf16 and amp != 1:
+            raise hip.CatreHipError("bf16 activation rows are read by the bf16-operand row GEMMs only")
         hip.check(lib.catre_op_gemm_rows_nr(hip.ptr(dy), dy.stride(0), hip.ptr(xmask),
                                             xmask.stride(0) if xmask is not None else 0, hip.ptr(wp), None, hip.ptr(mask),
                                             mask.stride(0), hip.ptr(mask_rows), hip.ptr(dx), K, cap, K, J, 0, hip.ptr(count),
@@ -661,13 +664,15 @@ def _wgrad_n(dy, x, ymask, count, amp=0, x_rows=None):
     ws = _ws(lib.catre_op_gemm_tn_bias_ws_bytes(J, K, cap), dy.device)
     if x_rows is not None:
         rows_bf16 = hip.ROWS_BF16 if x.dtype == torch.bfloat16 else 0
-        assert not rows_bf16 or amp == 1, "bf16 activation rows are read by the bf16-operand weight-gradient kernel only"
+        if rows_bf16 and amp != 1:
+            raise hip.CatreHipError("bf16 activation rows are read by the bf16-operand weight-gradient kernel only")
         hip.check(lib.catre_op_gemm_tn_bias_nr(hip.ptr(dy), dy.stride(0), hip.ptr(ymask),
                                                ymask.stride(0) if ymask is not None else 0, hip.ptr(x), x.stride(0),
                                                hip.ptr(x_rows), hip.ptr(dw), hip.ptr(db), J, K, cap, 0, hip.ptr(ws), ws.numel(),
                                                hip.ptr(count), int(amp) | rows_bf16, _st(dy)), "catre_op_gemm_tn_bias_nr")
         return dw, db
-    assert x.dtype == torch.float32
+    if x.dtype != torch.float32:
+        raise hip.CatreHipError(f"catre_op_gemm_tn_bias_n reads fp32 rows, not {x.dtype}")
     hip.check(lib.catre_op_gemm_tn_bias_n(hip.ptr(dy), dy.stride(0), hip.ptr(ymask), ymask.stride(0) if ymask is not None else 0,
                                           hip.ptr(x), x.stride(0), hip.ptr(dw), hip.ptr(db), J, K, cap, 0, hip.ptr(ws),
                                           ws.numel(), hip.ptr(count), int(amp), _st(dy)), "catre_op_gemm_tn_bias_n")
@@ -707,6 +712,8 @@ def _pooled_chain_backward(ctx, dg, merge):
     -> (dx, dw1, db1, dw2, db2, dw3, db3)."""
     x, w1, w2, w3, y1, y2, idx, gout = ctx.saved_tensors[:8]
     if y1 is None:
+        if merge is not None:
+            raise hip.CatreHipError("pooled chain: the recompute backward merges no other gradients (no saved rows)")
         return _pooled_chain_backward_recompute(ctx, dg)
     B, N, M = ctx.dims
     lib = hip.load()
@@ -725,7 +732,8 @@ def _pooled_chain_backward(ctx, dg, merge):
     # (y1 / y2 as bf16 rows: what the autocast encoder forward saves - the `_h` forms of the two pooled-layer kernels and
     # the CATRE_ROWS_BF16 flag of the row GEMMs below read them in place)
     hb = y2.dtype == torch.bfloat16
-    assert hb == (y1.dtype == torch.bfloat16)
+    if hb != (y1.dtype == torch.bfloat16):
+        raise hip.CatreHipError(f"pooled chain: saved rows of two dtypes ({y1.dtype}, {y2.dtype})")
     fn_w, fn_x = ((lib.catre_op_maxlin_bwd_w_h, lib.catre_op_maxlin_bwd_x_compact_h) if hb
                   else (lib.catre_op_maxlin_bwd_w, lib.catre_op_maxlin_bwd_x_compact))
     hip.check(fn_w(hip.ptr(dg), hip.ptr(idx), hip.ptr(y2), y2.stride(0), hip.ptr(dw3), hip.ptr(db3), C, J3, K3, _st(dg)),
@@ -846,6 +854,8 @@ class _PointfeatHub(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, x, w1, b1, w2, b2, w3, b3, B, N, M, y1, y2, g, idx, obj_copy=True):
+        if y1 is None:
+            raise hip.CatreHipError("pointfeat hub: needs the trunk's saved activation rows")
         lib = hip.load()
         xc = _c(x)
         J, C = xc.shape[1], (2 * B if M > 0 else B)
@@ -880,14 +890,7 @@ def pointfeat_hub(x, w1, b1, w2, b2, w3, b3, B, N, M, pre, obj_copy=True):
 
 
 def pooled_chain_ok(x, w1, w2, w3, N, M):
-    """Shapes the row-sparse chain takes (the encoder's three conv stacks at N, M multiples of 64; every compute mode)."""
-    if N % 64 or M % 64 or max(N, M) > 4096:
-        return False
-    j1, j2, j3 = w1.shape[0], w2.shape[0], w3.shape[0]
-    k1 = w1.reshape(j1, -1).shape[1]
-    if x.requires_grad and not _tiled_gemm_ok(1, k1, j1, min_rows=0):
-        return False  # the chain's input gradient is a tiled row GEMM with K1 outputs: a differentiable 3-d input takes the layer-wise ops
-    return (j1 in (64, 128) and j2 in (128, 512) and j3 <= 1024 and j3 % 32 == 0 and (k1 <= 8 or k1 in (64, 128)))
+    return TR.pooled_chain_ok(x.requires_grad, TR.Stack(*_jk(w1), w2.shape[0], w3.shape[0]), N, M)
 
 
 def pooled_chain(x, w1, b1, w2, b2, w3, b3, relu_pool, B, N, M, pre):
@@ -1104,8 +1107,7 @@ class _RotLinear(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None
 
 
-def _rot_linear_ok(R, J, K, N, M):
-    return N % 64 == 0 and M % 64 == 0 and _tiled_gemm_ok(R, J, K, min_rows=64) and K % 8 == 0
+_rot_linear_ok = TR.rot_linear_ok
 
 
 def linear_cloudbias(x, w, bias, B, N, M, with_gn_partials=False, pre=None):
@@ -1449,14 +1451,12 @@ class _RotHeadPairLP(torch.autograd.Function):
 
 
 def rot_head_pair_lp(x, head_x, head_y, B, N, M, x_cm=False):
-    """head_x / head_y: (w0, bias2d, g0, be0, w1, b1, g1, be1, wn, bn, wp, bp) of the two RotHeads -> (out_x, out_y)."""
+    """head_x / head_y: a train_forward.RotHeadW each -> (out_x, out_y)."""
     return _RotHeadPairLP.apply(x, *head_x, *head_y, B, N, M, x_cm)
 
 
 def rot_head_lp_ok(x, w0, w1, b1, N, M):
-    return (knobs().fused_lp_rot and knobs().lp_rot_bf16_rows and _amp() == 1 and x.shape[1] == 64 and w0.shape[0] == 256
-            and w0.reshape(256, -1).shape[1] == 64 and w1.shape[0] == 256 and w1.reshape(256, -1).shape[1] == 256
-            and b1 is not None and N % 64 == 0 and M % 64 == 0 and N > 0 and M > 0)
+    return TR.rot_head_lp_ok(_amp(), knobs(), x.shape[1], *_jk(w0), *_jk(w1), b1 is not None, N, M)
 
 
 def rot_head_lp(x, w0, bias2d, g0, be0, w1, b1, g1, be1, wn, bn, wp, bp, B, N, M, x_cm=False):
@@ -1467,8 +1467,7 @@ def rot_head_lp(x, w0, bias2d, g0, be0, w1, b1, g1, be1, wn, bn, wp, bp, B, N, M
 
 
 def rot_l1_tail_lp_ok(a, w, b, N, M):
-    return (knobs().fused_lp_rot and _amp() == 1 and a.shape[1] == 256 and w.shape[0] == 256 and w.reshape(256, -1).shape[1] == 256 and b is not None
-            and N % 64 == 0 and M % 64 == 0 and N > 0 and M > 0)
+    return TR.rot_l1_tail_lp_ok(_amp(), knobs(), a.shape[1], *_jk(w), b is not None, N, M)
 
 
 def rot_l1_tail_lp(a, w, b, gamma, beta, wn, bn, wp, bp, B, N, M, pre=None):
@@ -1533,9 +1532,7 @@ class _RotL0Block(torch.autograd.Function):
 
 
 def rot_l0_block_ok(x, w, N, M):
-    # autocast takes the node too (knob fused_lp_rot): bf16-operand forward, the one-pass backward
-    return ((_amp() == 0 or (_amp() == 1 and knobs().fused_lp_rot)) and w.shape[0] == 256 and w.reshape(256, -1).shape[1] == 64 and x.shape[1] == 64
-            and N % 64 == 0 and M % 64 == 0 and N > 0)
+    return TR.rot_l0_block_ok(_amp(), knobs(), x.shape[1], *_jk(w), N, M)
 
 
 def rot_l0_block(x, w, bias2d, gamma, beta, B, N, M, pre=None):
@@ -1590,8 +1587,7 @@ class _RotL1Block(torch.autograd.Function):
 
 
 def rot_l1_block_ok(a, w, N, M):
-    return (_amp() == 0 and a.shape[1] == 256 and w.shape[0] == 256 and w.reshape(256, -1).shape[1] == 256
-            and N % 64 == 0 and M % 64 == 0 and N > 0)
+    return TR.rot_l1_block_ok(_amp(), a.shape[1], *_jk(w), N, M)
 
 
 def rot_l1_block(a, w, b, gamma, beta, wn, bn, B, N, M):
@@ -1659,8 +1655,8 @@ class _RotHeads(torch.autograd.Function):
     over y1 (catre_op_gnp_gelu_neck_fwd_s, catre_op_rot_l1_bwd_s).  Backward: conv_p, then the per-head passes of
     _RotL1Block and _RotL0Block on the saved head slices; the two pointfeat gradients are summed here.
 
-    Per head h in (x, y) the inputs are: bias0 [2B,256] (global half of layer 0 + conv bias, per cloud), w0 [256,64] (local
-    half), GN0 gamma/beta, w1 [256,256], b1, GN1 gamma/beta, wn [3,256], bn [3] or None, conv_p weight [1,P,1] and bias.  ``pf_cm`` is pointfeat cloud-major
+    Per head h in (x, y) the inputs are, in the order of train_forward.RotHeadW: w0 [256,64] (local half of layer 0), bias0
+    [2B,256] (its global half + conv bias, per cloud), GN0 gamma/beta, w1 [256,256], b1, GN1 gamma/beta, wn [3,256], bn [3] or None, conv_p weight [1,P,1] and bias.  ``pf_cm`` is pointfeat cloud-major
     (what the kernels read); ``pf_obj`` the same rows object-major - the differentiable input and what the backward reads.
     ``prm`` / ``packed``: the runtime's parameter pointer array and fp32 weight image (heads included)."""
 
@@ -1676,7 +1672,7 @@ class _RotHeads(torch.autograd.Function):
         dev = pf_obj.device
         R, P = B * (N + M), N + M
         pf_cm, pf_obj = _c(pf_cm), _c(pf_obj)
-        bias0 = torch.stack([_c(hx[0]), _c(hy[0])])                               # [2, 2B, 256]
+        bias0 = torch.stack([_c(hx[1]), _c(hy[1])])                               # [2, 2B, 256]
         y0 = torch.empty(2, R, 256, dtype=torch.float32, device=dev)
         a0, y1 = torch.empty_like(y0), torch.empty_like(y0)
         part = torch.empty(2, R // 64, 32, 2, dtype=torch.float32, device=dev)
@@ -1690,7 +1686,7 @@ class _RotHeads(torch.autograd.Function):
         spart = torch.empty(2, R // 64, 3, 256, dtype=torch.float32, device=dev)
         y3 = torch.empty(2, R, 3, dtype=torch.float32, device=dev)
         for h, hd in enumerate((hx, hy)):
-            _, w0, g0, be0, w1, b1, g1, be1, wn, bn, wp, bp = hd
+            w0, _, g0, be0, w1, b1, g1, be1, wn, bn, wp, bp = hd
             wn, wv = _c(wn), _c(wp.reshape(-1))
             bnc = _c(bn) if bn is not None else None
             hip.check(lib.catre_op_gnp_gelu_neck_fwd_s(hip.ptr(y1[h]), hip.ptr(part[h]), hip.ptr(g1), hip.ptr(be1),
@@ -1706,7 +1702,7 @@ class _RotHeads(torch.autograd.Function):
         ctx.dims = (B, N, M)
         ctx.has_bn = (hx[9] is not None, hy[9] is not None)
         ctx.has_bp = (hx[11] is not None, hy[11] is not None)
-        ctx.wshapes = (hx[1].shape, hx[4].shape, hy[1].shape, hy[4].shape, hx[10].shape, hy[10].shape)
+        ctx.wshapes = (hx[0].shape, hx[4].shape, hy[0].shape, hy[4].shape, hx[10].shape, hy[10].shape)
         return outs[0], outs[1]
 
     @staticmethod
@@ -1729,7 +1725,7 @@ class _RotHeads(torch.autograd.Function):
                                                           x_cloud_major=ctx.x_cm)
             del da
             dxs.append(dx)
-            grads += [dbias0, dw0.view(ctx.wshapes[2 * h]), dg0, dbe0, dw1.view(ctx.wshapes[2 * h + 1]), db1, dpar[0], dpar[1],
+            grads += [dw0.view(ctx.wshapes[2 * h]), dbias0, dg0, dbe0, dw1.view(ctx.wshapes[2 * h + 1]), db1, dpar[0], dpar[1],
                       dpar[2:5], dbn, dwp.view(ctx.wshapes[4 + h]), dbp]
         return (None, dxs[0], None, None, None, None, None) + tuple(grads)
 
@@ -1755,12 +1751,11 @@ def rot_heads_forward(pf_cm, bias0x, bias0y, prm, packed, B, N, M, mode):
 
 
 def rot_heads_ok(pf_obj, N, M):
-    return _amp() == 0 and pf_obj.shape[1] == 64 and N % 64 == 0 and M % 64 == 0 and N > 0 and M > 0
+    return TR.rot_heads_ok(_amp(), pf_obj.shape[1], N, M)
 
 
 def rot_heads(pf_cm, pf_obj, prm, packed, B, N, M, head_x, head_y):
-    """head_* = (bias0, w0_local, gn0_w, gn0_b, w1, b1, gn1_w, gn1_b, wn3, bn3, conv_p_w, conv_p_b) -> the two heads'
-    conv_p outputs, each [B, 3] (columns >= rot_dim are zero)."""
+    """head_*: a train_forward.RotHeadW each -> the two heads' conv_p outputs, each [B, 3] (columns >= rot_dim are zero)."""
     assert len(head_x) == _RotHeads.NH and len(head_y) == _RotHeads.NH
     return _RotHeads.apply(pf_cm, pf_obj, prm, packed, B, N, M, *head_x, *head_y)
 
