@@ -242,6 +242,12 @@ _SIGS = {
     "catre_pclf_sample": (_I, [_P, _P, _P, _P, _P, _SZ, _P, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
     "catre_pclf_fps": (_I, [_P, _P, _P, _P, _SZ, _I, _I, _I, _I, _I, _P, _I, _P, _P]),
     "catre_depth_augment": (_I, [_P, _I, ctypes.c_float, _P, _I, _P, _P, _P, ctypes.c_uint64, _P, _I, _I, _I, _P]),
+    # initial poses from a NOCS map (include/catre_hip.h "batched RANSAC Umeyama", catre_amd/nocs_align.py)
+    "catre_umeyama": (_I, [_P, _P, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
+    "catre_nocs_align_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "catre_nocs_align": (_I, [_P, _P, _P, _P, ctypes.c_uint64, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _SZ]
+                         + [_P] * 9),
+    "catre_nocs_align_draws": (_I, [_P, ctypes.c_uint64, _P, _I, _I, _P, _P]),
     "catre_loss_fwd": (_I, [_P] * 15 + [_I, _I, _I, _P]),
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),

@@ -924,6 +924,56 @@ int catre_depth_augment(const void* depth_in, int in_is_u16, float depth_div, co
                         int use_draws, const double* draw_fill, const double* draw_keep, const double* draw_gauss,
                         unsigned long long seed, float* depth_out, int F, int H, int W, void* stream);
 
+/* ---- initial poses from a NOCS coordinate map: batched RANSAC Umeyama ------------------------------------- */
+
+/* The similarity (scale s, rotation R, translation t) that takes NOCS coordinates onto camera points, as the reference
+ * computes it per instance on the CPU (preprocess/pose_data.py: estimateSimilarityUmeyama :56-87,
+ * estimateSimilarityTransform :109-165, fallback of align_nocs_to_depth :38-47) - for I instances at once.
+ * src [I,Nmax,3] fp32 (device): NOCS coordinates in [-0.5, 0.5]; dst [I,Nmax,3] fp32 (device): camera points, in the
+ * unit t is wanted in; counts [I] int32 (device, NULL = Nmax everywhere): instance i uses its first counts[i] rows, the
+ * others are never read (a count outside [0, Nmax] selects nothing).  Arithmetic is fp64; outputs (device): scale [I],
+ * R [I,3,3] row-major, t [I,3] float64.  Nothing is copied to the host and nothing waits: all work is ordered on
+ * `stream`.  Nmax * 3 < 2^31.
+ *
+ * catre_umeyama: the plain least-squares fit  C = (1/m) sum (dst - mu_t)(src - mu_s)^T = U diag(D) V^T (D descending;
+ * if det(U) det(V) < 0, D[2] and U[:,2] are negated), R = U V^T, s = sum(D) / sum_axes var(src) (population variance),
+ * t = mu_t - s R mu_s, over the rows k < counts[i] with mask[i][k] != 0 (mask [I,Nmax] bytes, device, NULL = all).
+ * valid_out [I] int32 (optional): 0 - and s = 1, R = I, t = 0 - where no row is kept or the result is not finite. */
+int catre_umeyama(const float* src, const float* dst, const int32_t* counts, const unsigned char* mask, int I, int Nmax,
+                  double* scale_out, double* R_out, double* t_out, int32_t* valid_out, void* stream);
+
+/* catre_nocs_align: RANSAC around that fit.  With n = counts[i] and InlierT = 2 max_k |src_k - mean(src)| / 10, for
+ * it = 0 .. max_iter - 1: five indices in [0, n) with replacement -> (s_h, R_h, t_h) = the fit of those five pairs; the
+ * inliers are the k with |dst_k - (s_h R_h src_k + t_h)| < s_h InlierT (strict); the hypothesis replaces the best one if
+ * it has strictly more inliers; the loop stops after this iteration if 1 - (1 - best^5)^it > confidence (best = inliers
+ * of the best hypothesis / n; zero-based it, so never after iteration 0).  If best < min_inlier_ratio the instance is
+ * invalid: s = 1, R = I, t = 0, valid = 0 (what the reference's caller substitutes).  Also invalid - the reference
+ * raises or returns NaN there, which is not reproduced - n < 5 and a non-finite value in the first n rows.  Otherwise the
+ * result is catre_umeyama over the inliers of the best hypothesis.  The reference's constants: max_iter 128, confidence
+ * 0.99, min_inlier_ratio 0.1.
+ * draws [I,max_iter,5] int32 (device): the indices, e.g. a replayed np.random.randint(n, size=5) stream - given the
+ * reference's draws the discrete outputs are the reference's (wherever no residual sits on its threshold and the
+ * 5-point covariances have sigma_2 > 0).  A draw outside [0, n) makes its hypothesis empty.
+ * draws == NULL: index j of iteration it = mulhi32(word j, n) of Philox4x32-10 at counter (keys[i] low word, high word,
+ * it, word block) under key `seed` (words 0..3 of block 0, word 0 of block 1); keys [I] int64 (device, NULL = 0..I-1).
+ * The bias of mulhi32 is at most n / 2^32 per index.  An instance's result depends on its rows, count, seed and key
+ * only: not on I, Nmax, its slot in the batch or the launch.
+ * Further outputs (device, int32 [I]): valid, n_inliers (of the best hypothesis; 0 if none had any), iters (iterations
+ * evaluated; 0 for n < 5 / non-finite input), best_it (-1: none); mask_out [I,Nmax] bytes (optional): the inlier set of
+ * the best hypothesis, zeros beyond counts[i] and where there is none.
+ * workspace: catre_nocs_align_workspace_bytes(I, Nmax, max_iter) bytes of device memory (0 for sizes <= 0 and
+ * max_iter outside 1..128).  Status: CATRE_ERR_BAD_ARG for a NULL array or a non-positive size (before anything is
+ * dereferenced), CATRE_ERR_UNSUPPORTED for max_iter outside 1..128, CATRE_ERR_WORKSPACE, CATRE_ERR_LAUNCH.
+ * catre_nocs_align_draws writes the indices the draws == NULL route uses to draws_out [I,max_iter,5] (counts required). */
+size_t catre_nocs_align_workspace_bytes(int I, int Nmax, int max_iter);
+int catre_nocs_align(const float* src, const float* dst, const int32_t* counts, const int32_t* draws,
+                     unsigned long long seed, const long long* keys, int I, int Nmax, int max_iter, double confidence,
+                     double min_inlier_ratio, void* workspace, size_t ws_bytes, double* scale_out, double* R_out,
+                     double* t_out, int32_t* valid_out, int32_t* n_inliers_out, int32_t* iters_out, int32_t* best_it_out,
+                     unsigned char* mask_out, void* stream);
+int catre_nocs_align_draws(const int32_t* counts, unsigned long long seed, const long long* keys, int I, int max_iter,
+                           int32_t* draws_out, void* stream);
+
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
