@@ -433,3 +433,20 @@ class NocsEvaluator:
         # host flattening / upload + kernels + download / host AP, seconds, of the last call
         self.timings = dict(flatten_s=t1 - t0, device_s=t2 - t1, ap_s=t3 - t2)
         return res
+
+
+def add_errors(pose_est, pose_gt, pts, scale_est=None, scale_gt=None, symmetric=False):
+    """ADD (``symmetric=False``) or ADD-S per instance on the device (``lib/pysixd/pose_error.py``: ``add`` :256-271,
+    ``adi`` :274-296): pose_est, pose_gt [I,3,4], pts [I,n,3] or [n,3] (model points, shared) fp32 on the device, optional
+    scale_est / scale_gt [I,3] applied to the points first -> [I] fp32, the mean distance from every model point under the
+    ground truth to the same point (ADD) or to the nearest point (ADD-S) of the model under the estimate - the set the
+    reference builds its KD-tree on.  One ``catre_nn_stats`` call (``tracking.nn_stats``), nothing read back."""
+    from .tracking import nn_stats
+
+    if not isinstance(pose_est, torch.Tensor) or pose_est.ndim != 3 or tuple(pose_est.shape[1:]) != (3, 4):
+        raise ValueError("pose_est: expected a [I,3,4] tensor")
+    I = pose_est.shape[0]
+    if isinstance(pts, torch.Tensor) and pts.ndim == 2:
+        pts = pts[None].expand(I, *pts.shape)
+    return nn_stats(pts, pts, src_pose=pose_gt, src_scale=scale_gt, dst_pose=pose_est, dst_scale=scale_est,
+                    paired=not symmetric).mean_d

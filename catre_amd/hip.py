@@ -248,6 +248,10 @@ _SIGS = {
     "catre_nocs_align": (_I, [_P, _P, _P, _P, ctypes.c_uint64, _P, _I, _I, _I, ctypes.c_double, ctypes.c_double, _P, _SZ]
                          + [_P] * 9),
     "catre_nocs_align_draws": (_I, [_P, ctypes.c_uint64, _P, _I, _I, _P, _P]),
+    # tracking (include/catre_hip.h "tracking: nearest-neighbour statistics and the track gate", catre_amd/tracking.py)
+    "catre_nn_stats_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "catre_nn_stats": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
+    "catre_track_gate": (_I, [_P] * 7 + [ctypes.c_float, _I, _I] + [_P] * 5),
     "catre_loss_fwd": (_I, [_P] * 15 + [_I, _I, _I, _P]),
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),

@@ -974,6 +974,44 @@ int catre_nocs_align(const float* src, const float* dst, const int32_t* counts, 
 int catre_nocs_align_draws(const int32_t* counts, unsigned long long seed, const long long* keys, int I, int max_iter,
                            int32_t* draws_out, void* stream);
 
+/* ---- tracking: nearest-neighbour statistics and the track gate ------------------------------------------- */
+
+/* catre_nn_stats: for I pairs of point sets, the distance from every src point to its nearest dst point.
+ * src [I,n_src,3], dst [I,n_dst,3] fp32 (device).  A point x of a set with (pose [I,3,4] row-major [R | t], scale [I,3])
+ * stands at R (s * x) + t - the prior branch of catre_pose_apply; a NULL pose is the identity, a NULL scale is 1.
+ * paired != 0: the neighbour of src point n is dst point n (n_src == n_dst; ADD of lib/pysixd/pose_error.py:256-271);
+ * paired == 0: the dst point at the smallest squared distance, the lowest index on an exact tie (ADD-S, :274-296).
+ * Squared distances are fp32 from coordinate differences: dx = px - qx, ..., fmaf(dx,dx, fmaf(dy,dy, dz*dz)).
+ * Outputs (device): mean_d [I] = mean over the src points of sqrt(d^2); inlier [I] (optional, needs tau) = the share of
+ * src points with d^2 <= tau[i]^2 (tau [I] fp32, device, same unit as the points; tau^2 is one fp32 product; equality is
+ * inside); nn_d [I,n_src] (optional) = the SQUARED distances; nn_j [I,n_src] int32 (optional) = the neighbours.
+ * The sum over src points is a fixed tree accumulated in double, without atomics: an instance's results depend on its own
+ * rows only - the same bits alone and inside any batch.  Non-finite input is not special-cased: a NaN src point or a NaN
+ * dst point 0 gives NaN in mean_d, a NaN dst point elsewhere is never a neighbour.
+ * ws: catre_nn_stats_workspace_bytes(I, n_src, n_dst) bytes of device memory (0 for a size < 1, n * 3 >= 2^31 or
+ * I * ceil(n_src / 256) >= 2^24: the launch has one 256-thread workgroup per instance and 256 src points and stays
+ * below 2^32 threads).  Two launches on `stream`, nothing read back.  Status, decided before any launch:
+ * CATRE_ERR_BAD_ARG (NULL src / dst / mean_d, inlier without tau, sizes as above), CATRE_ERR_UNSUPPORTED (paired with
+ * n_src != n_dst), CATRE_ERR_WORKSPACE (ws NULL or short). */
+size_t catre_nn_stats_workspace_bytes(int I, int n_src, int n_dst);
+int catre_nn_stats(const float* src, int n_src, const float* dst, int n_dst, const float* src_pose, const float* src_scale,
+                   const float* dst_pose, const float* dst_scale, int paired, const float* tau, int I, float* mean_d,
+                   float* inlier, float* nn_d, int32_t* nn_j, void* ws, size_t ws_bytes, void* stream);
+
+/* catre_track_gate: which pose a track carries into the next frame.  pose_new / scale_new: the refined estimate,
+ * pose_prev / scale_prev: what the frame started from ([I,3,4], [I,3] fp32); counts [I] int32: candidate pixels of the
+ * crop; inlier, mean_d [I]: catre_nn_stats of observed points -> posed prior.  status [I] int32 is a bit set:
+ *   CATRE_TRACK_EMPTY      counts[i] == 0
+ *   CATRE_TRACK_LOW_FIT    inlier[i] < min_inlier (equality passes)
+ *   CATRE_TRACK_NONFINITE  a NaN or infinity in pose_new, scale_new, inlier or mean_d
+ * status == 0: pose_out / scale_out = the new estimate, age[i] = 0.  Otherwise age[i] += 1 (age [I] int32, in/out) and
+ * the outputs are the previous estimate if `hold` != 0 or CATRE_TRACK_NONFINITE is set, else the new one.  The outputs
+ * must not overlap the inputs.  One launch, nothing read back.  CATRE_ERR_BAD_ARG: a NULL array, I < 1. */
+enum { CATRE_TRACK_EMPTY = 1, CATRE_TRACK_LOW_FIT = 2, CATRE_TRACK_NONFINITE = 4 };
+int catre_track_gate(const float* pose_new, const float* scale_new, const float* pose_prev, const float* scale_prev,
+                     const int32_t* counts, const float* inlier, const float* mean_d, float min_inlier, int hold, int I,
+                     float* pose_out, float* scale_out, int32_t* status, int32_t* age, void* stream);
+
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
