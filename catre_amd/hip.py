@@ -252,6 +252,9 @@ _SIGS = {
     "catre_nn_stats_workspace_bytes": (_SZ, [_I, _I, _I]),
     "catre_nn_stats": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "catre_track_gate": (_I, [_P] * 7 + [ctypes.c_float, _I, _I] + [_P] * 5),
+    # splat render of the posed prior (include/catre_hip.h "splat render of the posed prior", catre_amd/render.py)
+    "catre_splat_workspace_bytes": (_SZ, [_I, _I, _I]),
+    "catre_splat_render": (_I, [_P] * 7 + [ctypes.c_float, ctypes.c_float] + [_I] * 5 + [_P, _SZ] + [_P] * 8),
     "catre_loss_fwd": (_I, [_P] * 15 + [_I, _I, _I, _P]),
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),

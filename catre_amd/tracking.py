@@ -8,7 +8,8 @@ its initial estimate (the paper's tracking experiment; why the reference trains 
 * :func:`fit_score` - does the posed prior lie on the observed points?  Two calls: observed -> prior and prior -> observed.
 * :func:`track_gate` - ``catre_track_gate``: status bits, carried pose / scale, age.
 * :class:`Tracker` - ``pcl_prep.sample_frames`` -> ``model.refine`` -> :func:`fit_score` -> :func:`track_gate`, state on
-  the device, no device->host copy and a constant number of ABI calls per frame.
+  the device, no device->host copy and a constant number of ABI calls per frame.  ``crop="render"`` crops with the depth-consistent
+  mask of the carried pose's splat (``catre_amd/render.py``) instead of the ball alone.
 
 Two contracts: a ``Tracker.step`` is bit-identical to that composition written out by hand, and an instance's results do
 not depend on the batch around it (``nn_stats`` reduces in a fixed order, without atomics)."""
@@ -158,12 +159,22 @@ class Tracker:
     needs them.  ``num_points`` / ``ratio`` default to ``cfg.INPUT.NUM_PCL`` / ``cfg.INPUT.DEPTH_SAMPLE_BALL_RATIO`` (0.5
     where the config has none), ``n_iter`` to ``N_ITER_TEST``.  Frame t is sampled with seed ``seed + t``.
 
+    ``crop``: what ``step`` takes for an object's pixels when it is given neither masks nor labels.  ``"ball"`` (default):
+    every pixel with depth > 0 inside the ball.  ``"render"``: the pixels where the splat of the carried pose
+    (``render.splat_prior``) agrees with the frame's depth to within ``crop_delta`` metres - ``labels_fit``, which leaves out
+    a table the object stands on and a hand in front of it.  ``crop_delta`` defaults to 0.05 m, the floor the reference
+    puts under the ball radius (``cat_data_utils.py``): a parameter, looser than the 15 mm of the visibility test because
+    the object has moved since the carried pose.  ``rho_rel`` / ``r_max``: the splat's disc size (``render.splat_prior``).
+
     ``reset(pose0, scale0)`` sets the carried state (e.g. from ``nocs_align.init_from_frames``); ``step(depth, ...)``
     advances one frame; ``track(depth_seq, ...)`` loops it.  The only policy is the gate: no motion model, no
     re-detection."""
 
     def __init__(self, model, kps, K, mean_scales=None, num_points=None, ratio=None, n_iter=None, tau_rel=0.1, min_inlier=0.0,
-                 hold_on_lost=True, seed=0):
+                 hold_on_lost=True, seed=0, crop="ball", crop_delta=0.05, rho_rel=0.06, r_max=24.0):
+        if crop not in ("ball", "render"):
+            raise ValueError(f"crop={crop!r}: expected 'ball' or 'render'")
+        self.crop, self.crop_delta, self.rho_rel, self.r_max = crop, float(crop_delta), float(rho_rel), float(r_max)
         kps = _points(kps, "kps")
         I = kps.shape[0]
         mean_scales = _opt(mean_scales, "mean_scales", (I, 3))
@@ -185,6 +196,7 @@ class Tracker:
             raise ValueError(f"n_iter must be at least 1, got {self.n_iter}")
         self.tau_rel, self.min_inlier, self.hold_on_lost, self.seed = float(tau_rel), float(min_inlier), bool(hold_on_lost), int(seed)
         self._frame_of = [0] * I
+        self._label_ids = list(range(1, I + 1))
         self._zero_labels = None
         self.pose = self.scale = self.age = None
         self.t = 0
@@ -228,6 +240,10 @@ class Tracker:
         """One frame: depth [H,W] or [1,H,W] fp32 on the device (metres); the objects' pixels as ``masks`` [I,H,W], as
         ``labels`` [H,W] with ``label_of`` [I], or neither (every pixel with depth > 0 inside the ball is a candidate).
 
+        With ``crop="render"`` and neither masks nor labels, the pixels are ``labels_fit`` of the carried pose's splat against
+        this depth map (``delta = crop_delta``), and the dict gains ``splat_counts`` [I,5] (``render.Splat.counts``); giving
+        masks or labels in that mode is a ``ValueError``.
+
         Crops and samples around the carried pose, refines ``n_iter`` times, scores the last iterate, gates.  ->
         ``dict(pose [I,3,4], scale [I,3]`` (what is carried on), ``pose_iters [n_iter+1,I,3,4], score`` (``FitScore`` of the
         last iterate), ``status [I], age [I]`` int32 (:func:`track_gate`), ``pcl [I,num_points,3])``, all on the device.
@@ -237,7 +253,16 @@ class Tracker:
         if self.pose is None:
             raise ValueError("Tracker.step before reset(pose0, scale0): there is no pose to crop around")
         depth = depth.reshape(1, *depth.shape[-2:])
-        masks, labels, label_of = self._pixels(depth, masks, labels, label_of)
+        splat = None
+        if self.crop == "render":
+            if masks is not None or labels is not None or label_of is not None:
+                raise ValueError('crop="render" renders the objects\' pixels itself: give neither masks nor labels')
+            from . import render
+            splat = render.splat_prior(self.kps, self.pose, self.scale, self._K_host, depth.shape[1:], rho_rel=self.rho_rel,
+                                       r_max=self.r_max, depth=depth, delta=self.crop_delta)
+            labels, label_of = splat.labels_fit, self._label_ids
+        else:
+            masks, labels, label_of = self._pixels(depth, masks, labels, label_of)
         pcl, _, counts = pcl_prep.sample_frames(depth, self._K_host, self._frame_of, self.pose, self.scale, masks=masks,
                                                 labels=labels, label_of=label_of, ratio=self.ratio, num_points=self.num_points,
                                                 use_ball=True, sample="device", seed=self.seed + self.t, return_pixels=True)
@@ -251,8 +276,11 @@ class Tracker:
                                               self.age, self.min_inlier, self.hold_on_lost)
         self.pose, self.scale, self.age = pose, scale, age
         self.t += 1
-        return {"pose": pose, "scale": scale, "pose_iters": torch.stack([out[f"pose_{i}"] for i in range(self.n_iter + 1)]),
-                "score": score, "status": status, "age": age, "pcl": pcl}
+        res = {"pose": pose, "scale": scale, "pose_iters": torch.stack([out[f"pose_{i}"] for i in range(self.n_iter + 1)]),
+               "score": score, "status": status, "age": age, "pcl": pcl}
+        if splat is not None:
+            res["splat_counts"] = splat.counts
+        return res
 
     def track(self, depth_seq, masks=None, labels=None, label_of=None):
         """``step`` over depth_seq [T,H,W]; ``masks`` [T,I,H,W] / ``labels`` [T,H,W] per frame (``label_of`` [I] for all).

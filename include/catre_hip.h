@@ -1012,6 +1012,52 @@ int catre_track_gate(const float* pose_new, const float* scale_new, const float*
                      const int32_t* counts, const float* inlier, const float* mean_d, float min_inlier, int hold, int I,
                      float* pose_out, float* scale_out, int32_t* status, int32_t* age, void* stream);
 
+/* ---- splat render of the posed prior: instance masks, a depth image and visibility ----------------------- */
+
+/* catre_splat_render: a z-buffered disc splat of I posed point priors into the F frames they are seen in.
+ * kps [I,M,3], pose [I,3,4], scale [I,3], rho [I] (metres: the disc radius of every splat of instance i), depth
+ * [F,H,W] (metres, may be NULL): fp32 on the device.  K = HOST [F][9], frame_of = HOST [I], as catre_pclf_candidates
+ * takes them, checked and staged the same way (one hipMemcpyAsync of F * 4 + I ints from pageable memory; nothing is
+ * ever copied back and nothing waits on the device's work; like that entry point the call cannot be captured into a
+ * graph, because of this copy).
+ * A point is p = R (s * x) + t (catre_nn_stats' arithmetic).  With the frame's fx, fy, cx, cy and an integer pixel being
+ * its own centre: u0 = fx * p.x / p.z + cx, v0 = fy * p.y / p.z + cy, r = min(fx * rho[i] / p.z, r_max) (r_max: pixels),
+ * each operation rounded to fp32 in that order.  A point with !(p.z > 0) or a non-finite u0, v0 or r draws nothing.  Its
+ * footprint is every pixel 0 <= u < W, 0 <= v < H with fmaf(du, du, dv * dv) <= r * r, du = u - u0, dv = v - v0
+ * (equality is inside; empty for a small r between pixel centres).  Every covered pixel keeps the minimum of the key
+ * (bits(p.z) << 32) | (i << 16) | m: the nearest depth, then the lower instance, then the lower point.  Integer min does
+ * not depend on the order of arrival: the outputs are bit-reproducible, and a frame's outputs do not depend on the other
+ * frames of the call.
+ * Outputs (device; labels, zbuf and counts are required, the others may be NULL):
+ *   labels [F,H,W] int32      i + 1, 0 = background
+ *   zbuf [F,H,W] fp32         the winner's p.z, 0 = background
+ *   point [F,H,W] int32       the winner's m, -1 = background
+ *   cls [F,H,W] uint8         CATRE_SPLAT_*: with an observed depth d and diff = zbuf - d (one fp32 subtraction)
+ *                               HOLE if !(d > 0), OCCLUDED if diff > delta, FREE if diff < -delta, else AGREE;
+ *                             depth == NULL: every rendered pixel is AGREE.  lib/pysixd/visibility.py:9-41 with the visible
+ *                             set split: its bop18 mask is AGREE | FREE, its bop19 mask AGREE | FREE | HOLE
+ *   labels_fit [F,H,W] int32  labels where cls == AGREE, else 0
+ *   counts [I,5] int32        pixels instance i won, then how many of them are AGREE, OCCLUDED, FREE, HOLE (column = class)
+ *   vis [I,M] uint8           1 iff the point was drawn, its centre pixel (rintf(u0), rintf(v0)) is inside the image,
+ *                             labels there is i + 1, p.z - zbuf <= delta there and the pixel is not OCCLUDED
+ * workspace: catre_splat_workspace_bytes(F, H, W) bytes of device memory (0 for a size < 1 or F * H * W >= 2^30).
+ * Launches on `stream`: clear, splat, resolve, and visible if vis != NULL - the same for any I and F.
+ * Status, decided before any launch: CATRE_ERR_BAD_ARG (a NULL required array, a size < 1, F * H * W >= 2^30, r_max
+ * negative or NaN, delta NaN, frame_of[i] outside [0, F), fx or fy zero or NaN), CATRE_ERR_UNSUPPORTED (I > 65535 or
+ * M > 65536: the key holds 16 bits of each), CATRE_ERR_WORKSPACE (workspace NULL or short). */
+enum {
+  CATRE_SPLAT_BACKGROUND = 0,
+  CATRE_SPLAT_AGREE = 1,
+  CATRE_SPLAT_OCCLUDED = 2,
+  CATRE_SPLAT_FREE = 3,
+  CATRE_SPLAT_HOLE = 4
+};
+size_t catre_splat_workspace_bytes(int F, int H, int W);
+int catre_splat_render(const float* kps, const float* pose, const float* scale, const float* rho, const float* depth,
+                       const float* K, const int32_t* frame_of, float r_max, float delta, int F, int I, int M, int H, int W,
+                       void* workspace, size_t ws_bytes, int32_t* labels, float* zbuf, int32_t* point, unsigned char* cls,
+                       int32_t* labels_fit, int32_t* counts, unsigned char* vis, void* stream);
+
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
