@@ -1609,6 +1609,7 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 #include "catre_align.h"
 #include "catre_track.h"
 #include "catre_render.h"
+#include "catre_bop.h"
 #include "catre_loss.h"
 #include "catre_eval.h"
 
@@ -2991,6 +2992,7 @@ int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, si
 #include "catre_align_api.inc"
 #include "catre_track_api.inc"
 #include "catre_render_api.inc"
+#include "catre_bop_api.inc"
 
 // ---- row f1: training loss ---------------------------------------------------------------------------------
 // One implementation behind both generations of entry points: nl loss slots (LOSS_NL: losses[6 + 14], part rows of

@@ -255,6 +255,10 @@ _SIGS = {
     # splat render of the posed prior (include/catre_hip.h "splat render of the posed prior", catre_amd/render.py)
     "catre_splat_workspace_bytes": (_SZ, [_I, _I, _I]),
     "catre_splat_render": (_I, [_P] * 7 + [ctypes.c_float, ctypes.c_float] + [_I] * 5 + [_P, _SZ] + [_P] * 8),
+    # BOP pose errors (include/catre_hip.h "BOP pose errors: MSSD, MSPD, proj_sym and VSD", catre_amd/pose_errors.py)
+    "catre_sym_err_workspace_bytes": (_SZ, [_I, _I]),
+    "catre_sym_err": (_I, [_P, _I, _I] + [_P] * 8 + [_I] * 4 + [_P, _SZ] + [_P] * 4),
+    "catre_vsd": (_I, [_P] * 8 + [ctypes.c_float] + [_I] * 8 + [_P] * 3),
     "catre_loss_fwd": (_I, [_P] * 15 + [_I, _I, _I, _P]),
     "catre_loss_bwd": (_I, [_P] * 14 + [_I, _I, _I, _P]),
     "catre_loss_fwd_sums": (_I, [_P] * 16 + [_I, _P, _I, _I, _I, _P]),

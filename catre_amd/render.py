@@ -35,7 +35,8 @@ def abi_call_count():
 
 
 def _check_args(kps, poses, scales, K, size, frame_of, n_frames, depth, rho=None):
-    """Shapes (``ValueError``), before the device is touched -> (I, M, F, H, W, frame_of list, K [F,3,3] on the host)."""
+    """Shapes (``ValueError``), before the device is touched -> (I, M, F, H, W, frame_of list, K [F,3,3] on the host).
+    ``pose_errors.vsd_prior`` calls this too, by keyword, to refuse both of its renders before the first: keep the names."""
     kps = tracking._points(kps, "kps")
     I, M = kps.shape[0], kps.shape[1]
     if tracking._opt(poses, "poses", (I, 3, 4)) is None or tracking._opt(scales, "scales", (I, 3)) is None:

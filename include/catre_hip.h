@@ -1058,6 +1058,57 @@ int catre_splat_render(const float* kps, const float* pose, const float* scale, 
                        void* workspace, size_t ws_bytes, int32_t* labels, float* zbuf, int32_t* point, unsigned char* cls,
                        int32_t* labels_fit, int32_t* counts, unsigned char* vis, void* stream);
 
+/* ---- BOP pose errors: MSSD, MSPD, proj_sym and VSD -------------------------------------------------------- */
+
+/* catre_sym_err: lib/pysixd/pose_error.py mssd (:131-153), mspd (:156-179) and proj_sym (:196-217) of I instances in one
+ * sweep.  pts [I,n,3] (pts_shared != 0: [n,3], the same model for all), pose_est, pose_gt [I,3,4] row-major [R | t],
+ * scale_est, scale_gt [I,3] (may be NULL: ones), K [I,3,3]: fp32 on the device.  The symmetry sets form a ragged table on
+ * the device: syms [S_tot,3,4] fp32 ([R_s | t_s]), sym_off [G+1] int32 (set g is rows sym_off[g] .. sym_off[g+1] - 1),
+ * sym_of [I] int32 (the set of instance i).  S_max >= the largest set any instance reads (the width of the tables).
+ * For symmetry s of instance i's set and model point p:
+ *   x_est = R_est (s_est * p) + t_est,  x_gt = R_gt (s_gt * (R_s p + t_s)) + t_gt  (without scales the reference's
+ *   R_gt R_s, R_gt t_s + t_gt),  pi(x) = (fx x / z + cx, fy y / z + cy) with K[i]
+ *   e3[i,s] = max_n |x_est - x_gt|,  e2[i,s] = max_n |pi(x_est) - pi(x_gt)|,  p2[i,s] = mean_n of the same pixel distance
+ * Arithmetic: the 3x4 composites are formed in double and rounded once per entry to fp32; a posed point is three fmas per
+ * coordinate starting at the translation; a projection is product, quotient, sum, each rounded; distances come from
+ * coordinate differences (fma(dx, dx, fma(dy, dy, dz dz)), fma(du, du, dv dv)), the maxima are taken over the squares and
+ * rooted once, the mean adds the fp32 roots in a fixed tree in double and is rounded to fp32 once.  An instance's results
+ * depend on its own rows only - the same bits alone and inside any batch.  Points behind the camera are not special.
+ * Outputs (device): err [3,I] fp32 = min_s of e3 (MSSD), e2 (MSPD), p2 (proj_sym); best [3,I] int32 = the index of the
+ * winning symmetry within the set, the lowest on an exact tie; tables [3,I,S_max] fp32 (may be NULL) = e3, e2, p2, +inf
+ * behind the end of a set.  A NaN in a pose, scale or point of an instance makes its three errors NaN (the reference's
+ * python min() over a list with NaNs depends on their order and is not reproduced).  An instance whose sym_of / sym_off
+ * entries lie outside the table gets NaN and index -1; nothing is read out of bounds.
+ * workspace: catre_sym_err_workspace_bytes(I, S_max) bytes of device memory (0 for a size < 1 or beyond what is indexed);
+ * not needed when `tables` is given.  Two launches on `stream`, nothing read back.  Status, decided before any launch:
+ * CATRE_ERR_BAD_ARG (a NULL required array, a size < 1, S_max > S_tot, n * 3 >= 2^31), CATRE_ERR_WORKSPACE. */
+size_t catre_sym_err_workspace_bytes(int I, int S_max);
+int catre_sym_err(const float* pts, int pts_shared, int n, const float* pose_est, const float* pose_gt, const float* scale_est,
+                  const float* scale_gt, const float* K, const float* syms, const int32_t* sym_off, const int32_t* sym_of,
+                  int G, int S_tot, int S_max, int I, void* workspace, size_t ws_bytes, float* err, int32_t* best,
+                  float* tables, void* stream);
+
+/* catre_vsd: lib/pysixd/pose_error.py vsd (:22-128, cost_type "step") after its two renders.  depth_est, depth_gt [I,h,w]
+ * (0: nothing rendered), depth_test [F,H,W], K [I,3,3] (of the full image): fp32 on the device; frame_of [I] int32 (device,
+ * NULL: frame 0), origin [I,2] int32 (device, (u0, v0); NULL: zeros): window pixel (col, row) of instance i is pixel
+ * (u0 + col, v0 + row) of frame frame_of[i]; window pixels outside the frame - and every pixel of an instance whose frame
+ * is outside [0, F) - are ignored.  diameter [I] fp64 (device, may be NULL: normalized_by_diameter off); taus = HOST [T]
+ * fp64, T <= CATRE_VSD_MAX_TAUS; delta: the visibility tolerance; visib_mode CATRE_VSD_BOP19 / _BOP18.
+ * Per pixel, in the reference's precisions: the distances sqrt(((x - cx) / fx d)^2 + ((y - cy) / fy d)^2 + d^2) in double,
+ * every operation rounded, added in that order (misc.py:628-647); the visibility masks (visibility.py:9-74) from
+ * fl32(dist_model) - fl32(dist_test) <= delta in fp32, dist_test == 0 and dist_model > 0 in double (the splat render's
+ * HOLE is !(d > 0): the two differ for a negative or NaN observed depth only); the cost |dist_gt - dist_est| / diameter
+ * >= tau in double on the intersection.
+ * Outputs (device): counts [I,2+T] int32 = pixels of the union, of the intersection, and of cost 1 per tau; errors [I,T]
+ * fp64 = (cost + union - inter) / union, 1.0 for an empty union.  Integer sums: bit-reproducible.
+ * A memset and two launches on `stream`, nothing read back.  Status, decided before any launch: CATRE_ERR_BAD_ARG (a NULL
+ * required array, a size < 1, h * w or H * W >= 2^30, a NaN delta or tau, an unknown visib_mode), CATRE_ERR_UNSUPPORTED
+ * (T > CATRE_VSD_MAX_TAUS). */
+enum { CATRE_VSD_BOP19 = 0, CATRE_VSD_BOP18 = 1, CATRE_VSD_MAX_TAUS = 16 };
+int catre_vsd(const float* depth_est, const float* depth_gt, const float* depth_test, const float* K, const int32_t* frame_of,
+              const int32_t* origin, const double* diameter, const double* taus, float delta, int visib_mode, int I, int h,
+              int w, int F, int H, int W, int T, int32_t* counts, double* errors, void* stream);
+
 /* ---- the training loss on the device --------------------------------------------------- */
 
 /* Flags of cfg.MODEL.CATRE.LOSS_CFG that CATRE_disR_shared.catre_loss reads
