@@ -66,10 +66,10 @@ __device__ __forceinline__ void align_swap(double& a, double& b) {
 }
 
 // C (c_rc: row r = target axis, column c = source axis), var = sum over axes of the population variance of S,
-// mu_s, mu_t -> the similarity
-__device__ __forceinline__ AlignFit align_solve(double c00, double c01, double c02, double c10, double c11, double c12,
-                                                double c20, double c21, double c22, double var, double msx, double msy,
-                                                double msz, double mtx, double mty, double mtz) {
+// mu_s, mu_t -> the similarity; sv0 >= sv1: the two largest singular values of C (the rotation is unique iff sv1 > 0)
+__device__ __forceinline__ AlignFit align_solve_sv(double c00, double c01, double c02, double c10, double c11, double c12,
+                                                   double c20, double c21, double c22, double var, double msx, double msy,
+                                                   double msz, double mtx, double mty, double mtz, double& sv0, double& sv1) {
   // columns of C
   double a0x = c00, a0y = c10, a0z = c20, a1x = c01, a1y = c11, a1z = c21, a2x = c02, a2y = c12, a2z = c22;
   double v0x = 1.0, v0y = 0.0, v0z = 0.0, v1x = 0.0, v1y = 1.0, v1z = 0.0, v2x = 0.0, v2y = 0.0, v2z = 1.0;
@@ -105,7 +105,15 @@ __device__ __forceinline__ AlignFit align_solve(double c00, double c01, double c
   f.t0 = mtx - f.s * (f.r00 * msx + f.r01 * msy + f.r02 * msz);
   f.t1 = mty - f.s * (f.r10 * msx + f.r11 * msy + f.r12 * msz);
   f.t2 = mtz - f.s * (f.r20 * msx + f.r21 * msy + f.r22 * msz);
+  sv0 = s0, sv1 = s1;
   return f;
+}
+
+__device__ __forceinline__ AlignFit align_solve(double c00, double c01, double c02, double c10, double c11, double c12,
+                                                double c20, double c21, double c22, double var, double msx, double msy,
+                                                double msz, double mtx, double mty, double mtz) {
+  double sv0, sv1;
+  return align_solve_sv(c00, c01, c02, c10, c11, c12, c20, c21, c22, var, msx, msy, msz, mtx, mty, mtz, sv0, sv1);
 }
 
 __device__ __forceinline__ bool align_finite(const AlignFit& f) {

@@ -1608,6 +1608,7 @@ __global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF1
 #include "catre_pclf.h"
 #include "catre_align.h"
 #include "catre_track.h"
+#include "catre_icp.h"
 #include "catre_render.h"
 #include "catre_bop.h"
 #include "catre_loss.h"
@@ -2991,6 +2992,7 @@ int catre_pcl_fps(const float* depth, const float* K9, const void* workspace, si
 #include "catre_pclf_api.inc"
 #include "catre_align_api.inc"
 #include "catre_track_api.inc"
+#include "catre_icp_api.inc"
 #include "catre_render_api.inc"
 #include "catre_bop_api.inc"
 

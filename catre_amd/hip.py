@@ -252,6 +252,10 @@ _SIGS = {
     "catre_nn_stats_workspace_bytes": (_SZ, [_I, _I, _I]),
     "catre_nn_stats": (_I, [_P, _I, _P, _I, _P, _P, _P, _P, _I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     "catre_track_gate": (_I, [_P] * 7 + [ctypes.c_float, _I, _I] + [_P] * 5),
+    # trimmed ICP (include/catre_hip.h "trimmed ICP", catre_amd/icp.py)
+    "catre_icp_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "catre_icp_step": (_I, [_P, _I, _P, _P, _I] + [_P] * 5 + [ctypes.c_float, _I, _I, _I] + [_P] * 7),
+    "catre_icp": (_I, [_P, _I, _P, _P, _I, _P, _P, _P, ctypes.c_float, _I, _I, _I] + [_P] * 6 + [_SZ, _P]),
     # splat render of the posed prior (include/catre_hip.h "splat render of the posed prior", catre_amd/render.py)
     "catre_splat_workspace_bytes": (_SZ, [_I, _I, _I]),
     "catre_splat_render": (_I, [_P] * 7 + [ctypes.c_float, ctypes.c_float] + [_I] * 5 + [_P, _SZ] + [_P] * 8),

@@ -7,7 +7,8 @@ its initial estimate (the paper's tracking experiment; why the reference trains 
   (``evaluation.add_errors``).
 * :func:`fit_score` - does the posed prior lie on the observed points?  Two calls: observed -> prior and prior -> observed.
 * :func:`track_gate` - ``catre_track_gate``: status bits, carried pose / scale, age.
-* :class:`Tracker` - ``pcl_prep.sample_frames`` -> ``model.refine`` -> :func:`fit_score` -> :func:`track_gate`, state on
+* :class:`Tracker` - ``pcl_prep.sample_frames`` -> ``model.refine`` -> :func:`fit_score` (-> with ``recover="icp"`` the
+  trimmed-ICP candidate of ``catre_amd/icp.py`` and its score) -> :func:`track_gate`, state on
   the device, no device->host copy and a constant number of ABI calls per frame.  ``crop="render"`` crops with the depth-consistent
   mask of the carried pose's splat (``catre_amd/render.py``) instead of the ball alone.
 
@@ -167,11 +168,22 @@ class Tracker:
     the object has moved since the carried pose.  ``rho_rel`` / ``r_max``: the splat's disc size (``render.splat_prior``).
 
     ``reset(pose0, scale0)`` sets the carried state (e.g. from ``nocs_align.init_from_frames``); ``step(depth, ...)``
-    advances one frame; ``track(depth_seq, ...)`` loops it.  The only policy is the gate: no motion model, no
-    re-detection."""
+    advances one frame; ``track(depth_seq, ...)`` loops it.
+
+    ``recover``: None (default) - the only policy is the gate, and a track whose refine goes wrong holds its last good pose.
+    ``"icp"`` - every step also runs ``recover_iters`` rigid trimmed-ICP iterations (``catre_amd/icp.py``, ``trim =
+    recover_trim``) from the CARRIED pose and scale on the same sampled points, scores that candidate as the refined pose
+    is scored, and takes it where ICP raised no status bit and the refined pose does not reach its ``inlier_obs`` (a NaN
+    refine score takes the candidate); then the unchanged gate.  No motion model, no re-detection."""
 
     def __init__(self, model, kps, K, mean_scales=None, num_points=None, ratio=None, n_iter=None, tau_rel=0.1, min_inlier=0.0,
-                 hold_on_lost=True, seed=0, crop="ball", crop_delta=0.05, rho_rel=0.06, r_max=24.0):
+                 hold_on_lost=True, seed=0, crop="ball", crop_delta=0.05, rho_rel=0.06, r_max=24.0, recover=None, recover_iters=20,
+                 recover_trim=0.7):
+        if recover not in (None, "icp"):
+            raise ValueError(f"recover={recover!r}: expected None or 'icp'")
+        self.recover, self.recover_iters, self.recover_trim = recover, int(recover_iters), float(recover_trim)
+        if recover is not None and (self.recover_iters < 0 or not 0.0 < self.recover_trim <= 1.0):
+            raise ValueError(f"recover_iters must be >= 0 and recover_trim in (0, 1], got {recover_iters} and {recover_trim}")
         if crop not in ("ball", "render"):
             raise ValueError(f"crop={crop!r}: expected 'ball' or 'render'")
         self.crop, self.crop_delta, self.rho_rel, self.r_max = crop, float(crop_delta), float(rho_rel), float(r_max)
@@ -247,6 +259,8 @@ class Tracker:
         Crops and samples around the carried pose, refines ``n_iter`` times, scores the last iterate, gates.  ->
         ``dict(pose [I,3,4], scale [I,3]`` (what is carried on), ``pose_iters [n_iter+1,I,3,4], score`` (``FitScore`` of the
         last iterate), ``status [I], age [I]`` int32 (:func:`track_gate`), ``pcl [I,num_points,3])``, all on the device.
+        With ``recover="icp"``: also ``recovered [I]`` bool (the ICP candidate was taken; ``score`` is then its score) and
+        ``icp`` (the ``ICPResult``); ``pose_iters`` stays the refine's.
         No device->host copy; the number of ABI calls does not depend on the frame."""
         if not isinstance(depth, torch.Tensor) or depth.ndim not in (2, 3) or (depth.ndim == 3 and depth.shape[0] != 1):
             raise ValueError("depth must be a [H,W] or [1,H,W] tensor")
@@ -272,6 +286,15 @@ class Tracker:
         out = self.model.refine(batch, n_iter=self.n_iter)
         pose_n, scale_n = out[f"pose_{self.n_iter}"], out[f"scale_{self.n_iter}"]
         score = fit_score(pcl, self.kps, pose_n, scale_n, self.tau_rel)
+        cand = recovered = None
+        if self.recover == "icp":
+            from . import icp as _icp
+            cand = _icp.icp(pcl, self.kps, self.pose, self.scale, n_iter=self.recover_iters, trim=self.recover_trim)
+            score_c = fit_score(pcl, self.kps, cand.pose, cand.scale, self.tau_rel)
+            recovered = (cand.status == 0) & ~(score.inlier_obs >= score_c.inlier_obs)
+            pose_n = torch.where(recovered[:, None, None], cand.pose, pose_n)
+            scale_n = torch.where(recovered[:, None], cand.scale, scale_n)
+            score = FitScore(*(torch.where(recovered, c, r) for c, r in zip(score_c, score)))
         pose, scale, status, age = track_gate(pose_n, scale_n, self.pose, self.scale, counts, score.inlier_obs, score.d_obs,
                                               self.age, self.min_inlier, self.hold_on_lost)
         self.pose, self.scale, self.age = pose, scale, age
@@ -280,6 +303,8 @@ class Tracker:
                "score": score, "status": status, "age": age, "pcl": pcl}
         if splat is not None:
             res["splat_counts"] = splat.counts
+        if cand is not None:
+            res["recovered"], res["icp"] = recovered, cand
         return res
 
     def track(self, depth_seq, masks=None, labels=None, label_of=None):
@@ -293,6 +318,7 @@ class Tracker:
                 raise ValueError(f"{name} must hold one entry per frame ({T})")
         steps = [self.step(depth_seq[f], None if masks is None else masks[f], None if labels is None else labels[f], label_of)
                  for f in range(T)]
-        out = {k: torch.stack([s[k] for s in steps]) for k in steps[0] if k != "score"}
-        out["score"] = FitScore(*(torch.stack([getattr(s["score"], f) for s in steps]) for f in FitScore._fields))
+        out = {k: torch.stack([s[k] for s in steps]) for k in steps[0] if k not in ("score", "icp")}
+        for key, nt in (("score", FitScore),) + ((("icp", type(steps[0]["icp"])),) if "icp" in steps[0] else ()):
+            out[key] = nt(*(torch.stack([getattr(s[key], f) for s in steps]) for f in nt._fields))
         return out

@@ -1012,6 +1012,55 @@ int catre_track_gate(const float* pose_new, const float* scale_new, const float*
                      const int32_t* counts, const float* inlier, const float* mean_d, float min_inlier, int hold, int I,
                      float* pose_out, float* scale_out, int32_t* status, int32_t* age, void* stream);
 
+/* ---- trimmed ICP: move a pose towards the observed points without the network ------------------------------ */
+
+/* Direction: observed point -> nearest posed prior point (the observation is partial and cluttered, the prior complete:
+ * the clutter is what gets trimmed).  pcl [I,n_src,3] observed points, kps [I,n_dst,3] prior, pose [I,3,4], scale [I,3]:
+ * fp32 on the device, a prior point x standing at R (s * x) + t as in catre_nn_stats.  counts [I] int32 (device, NULL =
+ * n_src everywhere): instance i uses its first counts[i] rows of pcl / nn_d2 / nn_j; k_icp_step never reads the others (a
+ * count outside [0, n_src] selects nothing).  tau [I] fp32 (device, optional): absolute, in the unit of the points.
+ *
+ * catre_icp_step: one step from given neighbours.  nn_d2 [I,n_src] fp32, nn_j [I,n_src] int32: exactly what
+ * catre_nn_stats writes to nn_d / nn_j for src = pcl, dst = kps, dst_pose = pose, dst_scale = scale.
+ *   candidates: rows k < counts[i] with 0 <= d2_k <= tau[i]^2 (one fp32 product, equality inside; tau NULL: every finite
+ *     d2_k) and 0 <= nn_j[k] < n_dst.  A NaN or infinite d2 is never a candidate, nor is any row under a NaN tau.  c = their
+ *     number.
+ *   kept set: the m = ceil((double)trim * c) candidates smallest under the total order (d2, then k): exact ties at the
+ *     boundary go to the lower indices.  trim in (0, 1].
+ *   fit, in fp64: source = prior point nn_j[k] at (pose, scale), target = pcl[k], over the kept rows; the least-squares
+ *     similarity of catre_umeyama (sigma, dR, dt); with_scale == 0: sigma = 1, dt = mu_T - dR mu_S.
+ *   update: R' = dR R, t' = sigma dR t + dt, s' = sigma s, each rounded once to fp32 -> pose_out [I,3,4], scale_out [I,3]
+ *     (pose_out / scale_out may be pose / scale themselves).
+ *   rmse [I] fp32 = sqrt(sum over kept of (double)d2 / m), summed in a fixed order (NaN when m == 0); kept [I] int32 = m;
+ *   mask [I,n_src] bytes (optional): 1 on the kept rows, 0 elsewhere (rows >= counts[i] included).
+ *   status [I] int32, in and out: the bits below are OR-ed into what it holds, so they are sticky over a sequence of steps.
+ *     CATRE_ICP_FEW         m < 3
+ *     CATRE_ICP_DEGENERATE  second singular value of the kept covariance <= 1e-12 * the first: no unique rotation
+ *     CATRE_ICP_NONFINITE   a NaN or infinity in the incoming pose or scale, or in the fit
+ *   With any bit set, now or earlier, pose_out / scale_out are pose / scale bit for bit; rmse and kept are still reported.
+ *   update == 0: rmse, kept and mask only; pose_out, scale_out and status are not touched (and may be NULL).
+ * One 256-thread workgroup per instance, one launch, nothing read back; an instance's outputs depend on its own rows only.
+ *
+ * catre_icp: for it = 0 .. n_iter: the two launches of catre_nn_stats at the current pose, then the step with
+ * update = (it < n_iter).  rmse, kept: [n_iter + 1, I]; row it is measured BEFORE update it, the last row is the fit of
+ * the returned pose.  status [I]: in and out as above (zero it for a fresh run).  tau stays fixed over the iterations.
+ * Bit-identical to the same sequence issued as catre_nn_stats (with nn_d, nn_j) and catre_icp_step calls.  No host
+ * synchronisation; 3 (n_iter + 1) launches (n_iter == 0: and two device-to-device copies of pose and scale).
+ * pose_out / scale_out must not overlap pose / scale.  ws: catre_icp_workspace_bytes(I, n_src, n_dst, n_iter) bytes of
+ * device memory (0 for sizes catre_nn_stats refuses and n_iter outside 0 .. CATRE_ICP_MAX_ITER).
+ * Status, decided before any launch: CATRE_ERR_BAD_ARG (a NULL required array, sizes as catre_nn_stats, trim outside
+ * (0, 1] or NaN, n_iter outside 0 .. CATRE_ICP_MAX_ITER), CATRE_ERR_WORKSPACE (ws NULL or short). */
+enum { CATRE_ICP_FEW = 1, CATRE_ICP_DEGENERATE = 2, CATRE_ICP_NONFINITE = 4 };
+#define CATRE_ICP_MAX_ITER 256
+size_t catre_icp_workspace_bytes(int I, int n_src, int n_dst, int n_iter);
+int catre_icp_step(const float* pcl, int n_src, const int32_t* counts, const float* kps, int n_dst, const float* pose,
+                   const float* scale, const float* nn_d2, const int32_t* nn_j, const float* tau, float trim, int with_scale,
+                   int update, int I, float* pose_out, float* scale_out, float* rmse, int32_t* kept, unsigned char* mask,
+                   int32_t* status, void* stream);
+int catre_icp(const float* pcl, int n_src, const int32_t* counts, const float* kps, int n_dst, const float* pose,
+              const float* scale, const float* tau, float trim, int with_scale, int n_iter, int I, float* pose_out,
+              float* scale_out, float* rmse, int32_t* kept, int32_t* status, void* ws, size_t ws_bytes, void* stream);
+
 /* ---- splat render of the posed prior: instance masks, a depth image and visibility ----------------------- */
 
 /* catre_splat_render: a z-buffered disc splat of I posed point priors into the F frames they are seen in.
