@@ -71,6 +71,25 @@ constexpr Switch SWITCHES[SW_COUNT] = {
     {"CATRE_SCREEN_F16_STN", CATRE_SCREEN_F16_STN_DEFAULT, sw(SW_SCREEN_F16) | POOLED_STN},  // k_stn*_pair_sp16 / _sr16 (screen_f16_ab.jsonl)
 };
 
+// `screen_epi` (catre_form_switch id SW_EPI, CATRE_SCREEN_EPI): the lean selection, list build and scan behind the fp16
+// screen's sweep (k_*_sr16e / k_*_sp16e; on, profiles/screen_epi_ab.jsonl).  It picks no other FORM - grid, run length and
+// screen arithmetic are those of `run_f16` / `screen_f16` - so it is no bit of the 13-bit form word the decision reads: ids
+// 10 - 12 stay the raw bits of the env-only STN arms, and this switch takes the first id behind the word.
+#ifndef CATRE_SCREEN_EPI_DEFAULT
+#define CATRE_SCREEN_EPI_DEFAULT true
+#endif
+constexpr int SW_EPI = SW_COUNT;
+inline std::atomic<int> g_screen_epi{-1};
+inline bool screen_epi() {
+  int v = g_screen_epi.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv("CATRE_SCREEN_EPI");
+    v = e ? atoi(e) != 0 : CATRE_SCREEN_EPI_DEFAULT;
+    g_screen_epi.store(v, std::memory_order_relaxed);
+  }
+  return v != 0;
+}
+
 // the raw switch word: read from the environment once, ids 0 - 9 then follow catre_form_switch
 inline std::atomic<int> g_forms{-1};
 inline int forms() {

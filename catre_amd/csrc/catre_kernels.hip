@@ -1824,9 +1824,19 @@ int launch_stn3d(const EncCall& c, const float* const* prm, const float* packed,
       RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
       break;
-    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_stn3d_pair_sr16, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_RUN_F16:
+      if (screen_epi())
+        hipLaunchKernelGGL(k_stn3d_pair_sr16e, grid, block, 0, c.st, run);
+      else
+        hipLaunchKernelGGL(k_stn3d_pair_sr16, grid, block, 0, c.st, run);
+      break;
     case CATRE_FORM_RUN: hipLaunchKernelGGL(k_stn3d_pair_sr, grid, block, 0, c.st, run); break;
-    case CATRE_FORM_SCREEN_F16: hipLaunchKernelGGL(k_stn3d_pair_sp16, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN_F16:  // (a probe keeps the kernel that carries the probe code)
+      if (screen_epi() && !probe_s)
+        hipLaunchKernelGGL(k_stn3d_pair_sp16e, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows);
+      else
+        hipLaunchKernelGGL(k_stn3d_pair_sp16, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows);
+      break;
     case CATRE_FORM_SCREEN_POOL: hipLaunchKernelGGL(k_stn3d_pair_sp, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
     case CATRE_FORM_SCREEN: hipLaunchKernelGGL(k_stn3d_pair_s, grid, block, 0, c.st, STN3D_ARGS(c, w), sc, probe_rows); break;
     case CATRE_FORM_PAIR: hipLaunchKernelGGL(k_stn3d_pair<false>, grid, block, 0, c.st, STN3D_ARGS(c, w)); break;
@@ -1857,9 +1867,19 @@ int launch_stnkd(const EncCall& c, const float* const* prm, const float* packed,
       RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
       break;
-    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_stnkd_pair_sr16, grid, block, 0, c.st, run); break;
+    case CATRE_FORM_RUN_F16:
+      if (screen_epi())
+        hipLaunchKernelGGL(k_stnkd_pair_sr16e, grid, block, 0, c.st, run);
+      else
+        hipLaunchKernelGGL(k_stnkd_pair_sr16, grid, block, 0, c.st, run);
+      break;
     case CATRE_FORM_RUN: hipLaunchKernelGGL(k_stnkd_pair_sr, grid, block, 0, c.st, run); break;
-    case CATRE_FORM_SCREEN_F16: hipLaunchKernelGGL(k_stnkd_pair_sp16, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
+    case CATRE_FORM_SCREEN_F16:
+      if (screen_epi() && !probe_s)
+        hipLaunchKernelGGL(k_stnkd_pair_sp16e, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows);
+      else
+        hipLaunchKernelGGL(k_stnkd_pair_sp16, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows);
+      break;
     case CATRE_FORM_SCREEN_POOL: hipLaunchKernelGGL(k_stnkd_pair_sp, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
     case CATRE_FORM_SCREEN: hipLaunchKernelGGL(k_stnkd_pair_s, grid, block, 0, c.st, STNKD_ARGS(c, w), sc, probe_rows); break;
     case CATRE_FORM_PAIR: hipLaunchKernelGGL(k_stnkd_pair<false>, grid, block, 0, c.st, STNKD_ARGS(c, w)); break;
@@ -1890,10 +1910,23 @@ int launch_trunk(const EncCall& c, const float* const* prm, const float* packed,
       RS_DISPATCH(d.row_split, LAUNCH_)
 #undef LAUNCH_
       break;
-    case CATRE_FORM_RUN_F16: hipLaunchKernelGGL(k_trunk4sr16, grid, dim3(256), 0, c.st, run); break;
+    case CATRE_FORM_RUN_F16:
+      // `screen_epi`: the lean kernels carry no probe code; a probe takes the one-tile kernel of the same screen arithmetic
+      // (S and eps are functions of the tile alone, and the cloud maxima of the tile maxima are the run form's)
+      if (screen_epi() && probe_s)
+        hipLaunchKernelGGL(k_trunk4sp16, dim3(c.B * (tiles_of(c.N) + tiles_of(c.M))), dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat),
+                           g_trunk_trace, sc);
+      else if (screen_epi())
+        hipLaunchKernelGGL(k_trunk4sr16e, grid, dim3(256), 0, c.st, run);
+      else
+        hipLaunchKernelGGL(k_trunk4sr16, grid, dim3(256), 0, c.st, run);
+      break;
     case CATRE_FORM_RUN: hipLaunchKernelGGL(k_trunk4sr, grid, dim3(256), 0, c.st, run); break;
     case CATRE_FORM_SCREEN_F16:
-      hipLaunchKernelGGL(k_trunk4sp16, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
+      if (screen_epi() && !probe_s)
+        hipLaunchKernelGGL(k_trunk4sp16e, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
+      else
+        hipLaunchKernelGGL(k_trunk4sp16, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
       break;
     case CATRE_FORM_SCREEN_POOL:
       hipLaunchKernelGGL(k_trunk4sp, grid, dim3(256), 0, c.st, TRUNK_ARGS(c, w, pointfeat), g_trunk_trace, sc);
@@ -2766,6 +2799,11 @@ int catre_refine_k_from(const float* pcl, const float* kps, const float* init_po
 
 
 int catre_form_switch(int id, int value) {
+  if (id == SW_EPI) {  // not a bit of the form word: it picks the epilogue of the fp16-screen forms, not a form
+    const int cur = screen_epi();
+    if (value >= 0) g_screen_epi.store(value != 0, std::memory_order_relaxed);
+    return cur;
+  }
   if (id < 0 || id >= SW_PUBLIC) return -1;
   const int bit = sw(id);
   const int cur = forms();
@@ -2799,6 +2837,10 @@ int catre_debug_knob(int id, int value) {
   if (id == 0) return hipMemcpyToSymbol(HIP_SYMBOL(g_dephase_cycles), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
   if (id == 1) return hipMemcpyToSymbol(HIP_SYMBOL(g_ablate), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
   if (id == 2) return hipMemcpyToSymbol(HIP_SYMBOL(g_screen_count_on), &value, sizeof(int)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
+  if (id == 3) {  // SCREEN_STAMP of catre_screen.h into the buffer of catre_debug_trunk_trace (>= 1 << 24 entries)
+    unsigned long long* t = value ? g_trunk_trace : nullptr;
+    return hipMemcpyToSymbol(HIP_SYMBOL(g_screen_trace), &t, sizeof(t)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
+  }
   return CATRE_ERR_BAD_ARG;
 #else
   (void)id;
@@ -2837,7 +2879,9 @@ int catre_debug_screen_counts(unsigned long long* out192, int reset) {
 int catre_debug_trunk_trace(void* device_buffer) {
 #ifdef CATRE_DEBUG_TRACE
   g_trunk_trace = (unsigned long long*)device_buffer;
-  return CATRE_OK;
+  // (the screened epilogues' sub-phase stamps need a larger buffer: off until catre_debug_knob 3 asks for them)
+  unsigned long long* none = nullptr;
+  return hipMemcpyToSymbol(HIP_SYMBOL(g_screen_trace), &none, sizeof(none)) == hipSuccess ? CATRE_OK : CATRE_ERR_LAUNCH;
 #else
   (void)device_buffer;
   return CATRE_ERR_UNSUPPORTED;  // product build: no stamps in the kernels (make TRACE=1 builds the instrumented library)

@@ -212,6 +212,36 @@ __device__ __forceinline__ T lane_get(T v, int src_lane) {
   return __builtin_bit_cast(T, __builtin_amdgcn_ds_bpermute(src_lane << 2, __builtin_bit_cast(int, v)));
 }
 
+// Inclusive prefix sum over the wave's 64 lanes on the DPP path: four row_shr steps inside each row of 16 lanes, then
+// row_bcast:15 into rows 1 and 3 and row_bcast:31 into rows 2 and 3.  No LDS round trip and no lane id; every lane active.
+__device__ __forceinline__ int wave_prefix_incl(int v) {
+  v += __builtin_amdgcn_update_dpp(0, v, 0x111, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x112, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x114, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x118, 0xf, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x142, 0xa, 0xf, false);
+  v += __builtin_amdgcn_update_dpp(0, v, 0x143, 0xc, 0xf, false);
+  return v;
+}
+
+// Sub-phase stamps of the screened epilogue, instrumented build only (profiles/trace_screen_epi.py; catre_debug_knob 3
+// turns them on): the buffer of catre_debug_trunk_trace, layer L at offset L << 22, [tile][8][8] like the trunk's stamps, wave w in the unused row 4 + w:
+// [0] entry, [1] behind the selection, [2] behind the list build, [3] behind the replay, [4] behind the scan, [5] end
+// (the last batch's, where a list filled up).  The buffer holds 1 << 24 entries in front of the rotation heads' stamps.
+#ifdef CATRE_DEBUG_TRACE
+__device__ unsigned long long* g_screen_trace = nullptr;
+#define SCREEN_STAMP(layer, tile, wave, i)                                                                    \
+  do {                                                                                                        \
+    unsigned long long* t_ = g_screen_trace;                                                                  \
+    if (t_ && lane == 0 && (tile) < (1 << 16))                                                                \
+      t_[((size_t)(layer) << 22) + ((size_t)(tile) * 8 + 4 + (wave)) * 8 + (i)] = __builtin_readcyclecounter(); \
+  } while (0)
+#else
+#define SCREEN_STAMP(layer, tile, wave, i) \
+  do {                                     \
+  } while (0)
+#endif
+
 // Row addressing of the fp32 LDS image a screened layer reads: SWZ = the XOR-swizzled [rows][C] image of the trunk (pitch
 // C, chunk c of row r at c ^ (r & 15)), otherwise a padded image of pitch `ld` (the STN kernels' [128][LD128]).
 // ||a(p)||_2 (rounded up) of the ROWS rows of the image -> na[ROWS]; NT threads, NT/ROWS per row
@@ -592,13 +622,33 @@ __device__ __forceinline__ void screen_replay_pool(const f32x4* __restrict__ wba
 // one batch on all but tie-heavy tiles, at most 32 (every channel has <= 64 entries, so a batch holds >= 8 channels).
 // RUN: frun[0 .. 1024) is the run's running maximum (pre-bias, the `best` of the tiles before this one; not read when
 // `first`): `best` starts from it and is written back.  The list may then be empty and the replay loop is skipped.
-template <int K, bool SWZ, int LAYER, bool RUN = false>
+// EPI (kernel-form switch `screen_epi`): the same lists, rounds and results with fewer LDS round trips - the lane's four
+// sets are read once in two 16-byte reads and masked by `start` afterwards, the prefix runs on the DPP path
+// (wave_prefix_incl), the batch total comes through v_readlane, and the scan walks the lane's entries - contiguous in the
+// list, channel after channel - in ONE loop of two reads a trip instead of four dependent loops.  (The list BUILD keeps its
+// four loops: one loop over the concatenated sets measured slower, profiles/experiments/screen_epi_one_loop.md.)
+template <int K, bool SWZ, int LAYER, bool RUN = false, bool EPI = false>
 __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbase, const float* x, int ld,
                                                   unsigned long long* sets, float* __restrict__ out,
                                                   const float* __restrict__ bias, int ch0, bool relu, int lane,
-                                                  float* frun = nullptr, bool first = true) {
+                                                  float* frun = nullptr, bool first = true, int tile = 0) {
   unsigned* list = reinterpret_cast<unsigned*>(sets + 256);
   float best[4] = {-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+  unsigned long long mset[4] = {0, 0, 0, 0};
+  if constexpr (EPI) {
+    const u32x4 s01 = *reinterpret_cast<const u32x4*>(sets + 4 * lane), s23 = *reinterpret_cast<const u32x4*>(sets + 4 * lane + 2);
+    mset[0] = (unsigned long long)s01[1] << 32 | s01[0];
+    mset[1] = (unsigned long long)s01[3] << 32 | s01[2];
+    mset[2] = (unsigned long long)s23[1] << 32 | s23[0];
+    mset[3] = (unsigned long long)s23[3] << 32 | s23[2];
+#ifdef CATRE_DEBUG_TRACE
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {  // (the selection of this form never holds a channel's whole set)
+      const int cj = __popcll(mset[j]);
+      SCREEN_COUNT(LAYER, cj < 31 ? cj : 31, 1ull);
+    }
+#endif
+  }
   if constexpr (RUN) {
     if (!first) {
       const f32x4 f = *reinterpret_cast<const f32x4*>(frun + ch0 + 4 * lane);
@@ -615,14 +665,18 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     int c[4], off[4], s = 0;
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      c[j] = 4 * lane + j >= start ? __popcll(sets[4 * lane + j]) : 0;
+      c[j] = 4 * lane + j >= start ? __popcll(EPI ? mset[j] : sets[4 * lane + j]) : 0;
       s += c[j];
     }
     int incl = s;
+    if constexpr (EPI) {
+      incl = wave_prefix_incl(s);
+    } else {
 #pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const int t = lane_get(incl, lane - o);
-      if (lane >= o) incl += t;
+      for (int o = 1; o < 64; o <<= 1) {
+        const int t = lane_get(incl, lane - o);
+        if (lane >= o) incl += t;
+      }
     }
     // channels whose inclusive prefix fits: a prefix [0, end) of the channels (those below `start` count 0 entries)
     int run = incl - s, end = 0, last[4];
@@ -634,12 +688,15 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
       end += __popcll(__ballot(run <= SCREEN_POOL_CAP));
     }
     const int sel = (end - 1) & 3;
-    const int total = lane_get(sel == 0 ? last[0] : sel == 1 ? last[1] : sel == 2 ? last[2] : last[3], (end - 1) >> 2);
+    const int lastsel = sel == 0 ? last[0] : sel == 1 ? last[1] : sel == 2 ? last[2] : last[3];
+    // (`end` is a sum of ballot counts: wave-uniform)
+    const int total = EPI ? __builtin_amdgcn_readlane(lastsel, __builtin_amdgcn_readfirstlane((end - 1) >> 2))
+                          : lane_get(lastsel, (end - 1) >> 2);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       const int cw = 4 * lane + j;
       if (cw >= start && cw < end) {
-        unsigned long long m = sets[cw];
+        unsigned long long m = EPI ? mset[j] : sets[cw];
         int o = off[j];
         while (m) {
           const int bit = __builtin_ctzll(m);
@@ -651,6 +708,7 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    SCREEN_STAMP(LAYER, tile, ch0 >> 8, 2);
 #pragma unroll 1
     for (int e0 = 0; e0 < total; e0 += 128) {
       if (total - e0 > 64)
@@ -660,14 +718,40 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    SCREEN_STAMP(LAYER, tile, ch0 >> 8, 3);
+    if constexpr (EPI) {
+      // the lane's entries of this batch are list[off[0] .. hi): channel j's end at lim[j] (a channel at or above `end`
+      // keeps its count but is not in the batch; one below `start` counts 0)
+      int lim[4], hi = off[0];
 #pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const int cw = 4 * lane + j;
-      if (cw >= start && cw < end)
-        for (int i = 0; i < c[j]; ++i) best[j] = fmaxf(best[j], __uint_as_float(list[off[j] + i]));
+      for (int j = 0; j < 4; ++j) {
+        hi += 4 * lane + j < end ? c[j] : 0;
+        lim[j] = hi;
+      }
+      for (int i = off[0]; i < hi; i += 2) {
+        const int i1 = i + 1 < SCREEN_POOL_CAP ? i + 1 : SCREEN_POOL_CAP - 1;  // (past the lane's last entry: dropped below)
+        const float v[2] = {__uint_as_float(list[i]), __uint_as_float(list[i1])};
+#pragma unroll
+        for (int e = 0; e < 2; ++e) {
+          const int q = i + e;
+          const bool t0 = q < lim[0], t1 = q < lim[1], t2 = q < lim[2], t3 = q < lim[3];
+          best[0] = fmaxf(best[0], t0 ? v[e] : -INFINITY);
+          best[1] = fmaxf(best[1], t1 && !t0 ? v[e] : -INFINITY);
+          best[2] = fmaxf(best[2], t2 && !t1 ? v[e] : -INFINITY);
+          best[3] = fmaxf(best[3], t3 && !t2 ? v[e] : -INFINITY);
+        }
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j) {
+        const int cw = 4 * lane + j;
+        if (cw >= start && cw < end)
+          for (int i = 0; i < c[j]; ++i) best[j] = fmaxf(best[j], __uint_as_float(list[off[j] + i]));
+      }
     }
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
+    SCREEN_STAMP(LAYER, tile, ch0 >> 8, 4);
 #ifdef CATRE_DEBUG_TRACE
     entries += total;
     rounds += (total + 63) >> 6;
@@ -689,6 +773,7 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
     if (relu) v[j] = fmaxf(v[j], 0.f);
   }
   *reinterpret_cast<f32x4*>(out + ch0 + 4 * lane) = v;
+  SCREEN_STAMP(LAYER, tile, ch0 >> 8, 5);
 #ifdef CATRE_DEBUG_TRACE
   if (lane == 0) {
     SCREEN_COUNT(LAYER, 32 + (rounds < 15 ? rounds : 15), 1ull);
@@ -713,7 +798,9 @@ __device__ __forceinline__ void screen_pool_store(const f32x4* __restrict__ wbas
 //          the same, `sets` then holds one set per channel at [mb * 32 + n]
 //   RUN  : (POOL only) the run form: frun = the run's running maximum, see screen_pool_store and the header
 //   F16  : acc holds the fp16 screen's SCALED values (ScreenPipeF16, tile scale exponent `sa`); see the header
-template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false, bool RUN = false, bool F16 = false>
+//   EPI  : (POOL and F16 only) the leaner selection, list build and scan of kernel-form switch `screen_epi`: the same
+//          candidate sets, lists and results; no probe (sc.probe_s is not read)
+template <int MB, int K, bool SWZ = true, int LAYER = 0, bool POOL = false, bool RUN = false, bool F16 = false, bool EPI = false>
 __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], const f32x4* __restrict__ wf,
                                                     const float* __restrict__ nw, const float* na, const float* x,
                                                     unsigned long long* sets, float* __restrict__ out,
@@ -722,8 +809,10 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
                                                     bool first = true, int sa = 0) {
   static_assert(POOL || !RUN, "the run form refines the pooled replay");
   static_assert(POOL || !F16, "the fp16 screen exists for the pooled forms");
+  static_assert(!EPI || (POOL && F16), "the lean epilogue exists for the pooled fp16-screen forms");
   constexpr int NKC8 = K / 64;
   const int n = lane & 31, h = lane >> 5;
+  if constexpr (POOL) SCREEN_STAMP(LAYER, tile, ch0 >> 8, 0);
   const int partner = (lane ^ 32) << 2;  // ds_bpermute address of the channel's other half-wave lane
   auto swap32 = [&](auto v) { return __builtin_bit_cast(decltype(v), __builtin_amdgcn_ds_bpermute(partner, __builtin_bit_cast(int, v))); };
   // first weight chunks of the replay: requested before the selection arithmetic
@@ -753,6 +842,65 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
         for (int mb = 0; mb < MB; ++mb) fc[mb] = frun[ch0 + mb * 32 + n];
       }
     }
+    if constexpr (EPI) {
+      // The same predicate with less work per accumulator: each is read once, eps and fl(S + eps) are computed once and the
+      // 32 upper values of the m-block wait in registers for L; the mask is built by shift-and-insert through the carry
+      // (compare into vcc, own = 2 own + vcc: two chains of 16, from bit 15 down, so that bit nb 16 + r keeps its meaning).
+      // Each half-wave writes its own 32-bit half of the channel's set; the exchange of L of m-block mb + 1 is in flight
+      // while m-block mb is compared.  No probe in this form: a probe call takes the kernels that carry the probe code.
+      float uwv[MB], dwv[MB], nwv[MB];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        uwv[mb] = sc.uw[ch0 + mb * 32 + n];
+        dwv[mb] = sc.uw[1024 + ch0 + mb * 32 + n];
+        nwv[mb] = nw[ch0 + mb * 32 + n];
+      }
+      const float ua = screen_pow2(sa < -60 ? 60 : -sa);
+      float hv[2][32], Lown[2], Loth[2];
+      auto pass1 = [&](int mb, float(&hi)[32]) {
+        float e1, e0;
+        screen_eps_coef_f16<K>(nwv[mb], uwv[mb], dwv[mb], ua, e1, e0);
+        const float u = uwv[mb] * ua;
+        float L = -INFINITY;
+        if constexpr (RUN) L = fc[mb];
+#pragma unroll
+        for (int nb = 0; nb < 2; ++nb)
+#pragma unroll
+          for (int r = 0; r < 16; ++r) {
+            const float a = acc[mb][nb][r], eps = fmaf(e1, na4[nb][r >> 2][r & 3], e0);
+            L = fmaxf(L, fmaf(a, u, -eps));
+            hi[nb * 16 + r] = fmaf(a, u, eps);
+          }
+        return L;
+      };
+      Lown[0] = pass1(0, hv[0]);
+      Loth[0] = swap32(Lown[0]);
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        const int cur = mb & 1;
+        if (mb + 1 < MB) {
+          Lown[cur ^ 1] = pass1(mb + 1, hv[cur ^ 1]);
+          Loth[cur ^ 1] = swap32(Lown[cur ^ 1]);
+        }
+        const float L = fmaxf(Lown[cur], Loth[cur]);
+        unsigned m1 = 0, m0 = 0;
+#pragma unroll
+        for (int r = 15; r >= 0; --r) {
+          asm("v_cmp_ge_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m1) : "v"(hv[cur][16 + r]), "v"(L) : "vcc");
+          asm("v_cmp_ge_f32 vcc, %1, %2\n\tv_addc_co_u32 %0, vcc, %0, %0, vcc" : "+v"(m0) : "v"(hv[cur][r]), "v"(L) : "vcc");
+        }
+        unsigned own = m1 << 16 | m0;
+        if (sa < -60 || !(uwv[mb] <= 0x1p60f)) own = 0xffffffffu;
+        own &= vmask;
+        // NaN inputs only, as below: the whole set is empty only where L is -inf (a finite L is some point's fl(S - eps),
+        // and that point's fl(S + eps) is not below it), so the other half is asked for there alone
+        if (L == -INFINITY) {
+          const unsigned other = swap32(own);
+          if ((own | other) == 0 && h == 0) own = 1;
+        }
+        reinterpret_cast<unsigned*>(sets)[2 * (mb * 32 + n) + h] = own;
+      }
+    } else {
     // candidates of the lane's channel as a 64-bit set: bit 32 h' + 16 nb + r, the same word in both half-waves
 #pragma unroll
     for (int mb = 0; mb < MB; ++mb) {
@@ -810,12 +958,14 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
         sets[mb * 64 + lane] = m64;
       }
     }
+    }
   }
   if constexpr (POOL) {
     static_assert(MB == 8, "lane l owns channels 4 l .. 4 l + 3 of the wave's 256");
     __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
     __builtin_amdgcn_wave_barrier();
-    screen_pool_store<K, SWZ, LAYER, RUN>(wf - n, x, ld, sets, out, bias, ch0, relu, lane, frun, first);
+    SCREEN_STAMP(LAYER, tile, ch0 >> 8, 1);
+    screen_pool_store<K, SWZ, LAYER, RUN, EPI>(wf - n, x, ld, sets, out, bias, ch0, relu, lane, frun, first, tile);
     return;
   }
 #ifdef CATRE_DEBUG_TRACE
@@ -888,7 +1038,7 @@ struct ScreenPipeSel { typedef A type; };
 template <class A, class B>
 struct ScreenPipeSel<false, A, B> { typedef B type; };
 
-template <bool POOL, bool RUN = false, bool F16 = false>
+template <bool POOL, bool RUN = false, bool F16 = false, bool EPI = false>
 struct Trunk4ScreenT {
   ScreenArgs sc;
   float* frun;  // run form: the run's 1024 running maxima (workspace), and whether this is the run's first tile
@@ -923,7 +1073,7 @@ struct Trunk4ScreenT {
     // the two) - the sweep above runs at exactly 256 VGPRs next to its 256 accumulators, and a lane id live across it is one
     // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
-    screen_select_store<8, 512, true, 0, POOL, RUN, F16>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
+    screen_select_store<8, 512, true, 0, POOL, RUN, F16, EPI>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
                                                          false, valid, tile, sc, lane, 512, frun, first, F16 ? sa : 0);
   }
 };
@@ -945,7 +1095,7 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
 }
 
 // the same kernel with the pooled replay (screen_pool_store); k_trunk4sp16: with the fp16 screen (`screen_f16`)
-#define TRUNK4SP_(NAME, F16)                                                                                              \
+#define TRUNK4SP_(NAME, F16, EPI)                                                                                            \
   __global__ __launch_bounds__(256) void NAME(                                                                            \
       catre_points P, const float* __restrict__ trans3, const float* __restrict__ trans64, const float* __restrict__ Wc1, \
       const float* __restrict__ bc1, const f32x4* __restrict__ wp2, const float* __restrict__ b2,                         \
@@ -953,13 +1103,14 @@ __global__ __launch_bounds__(256) void k_trunk4s(catre_points P, const float* __
       const float* __restrict__ b4, float* __restrict__ pm, float* __restrict__ pointfeat, int B, int N, int M,           \
       unsigned long long* __restrict__ trace, ScreenArgs sc) {                                                            \
     __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];                                                       \
-    Trunk4ScreenT<true, false, F16> tl;                                                                                   \
+    Trunk4ScreenT<true, false, F16, EPI> tl;                                                                                \
     tl.sc = sc;                                                                                                           \
     trunk4_body<false>(smem, P, trans3, trans64, Wc1, bc1, wp2, b2, wp3, b3, wp4, b4, pm, pointfeat, B, N, M, trace,      \
                        TrainSave{}, tl, blockIdx.x, threadIdx.x);                                                         \
   }
-TRUNK4SP_(k_trunk4sp, false)
-TRUNK4SP_(k_trunk4sp16, true)
+TRUNK4SP_(k_trunk4sp, false, false)
+TRUNK4SP_(k_trunk4sp16, true, false)
+TRUNK4SP_(k_trunk4sp16e, true, true)  // `screen_epi`: the lean epilogue, no probe
 #undef TRUNK4SP_
 
 // Run -> tiles.  Runs are enumerated like tiles, observed clouds first; a cloud of T tiles has ceil(T / S) runs of S
@@ -998,7 +1149,7 @@ struct TrunkRunArgs {
   int B, N, M, S;
 };
 
-template <bool F16>
+template <bool F16, bool EPI = false>
 __device__ __forceinline__ void trunk4sr_body() {
   __shared__ __attribute__((aligned(16))) float smem[TRUNK_SMEM];
   // The arguments are read from the kernel-argument segment afresh in every tile (the pointer passes through an empty
@@ -1017,7 +1168,7 @@ __device__ __forceinline__ void trunk4sr_body() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const TrunkRunArgs a = *(const TrunkRunArgs*)ap;  // (generic pointer for the copy; the loads stay scalar)
-    Trunk4ScreenT<true, true, F16> tl;
+    Trunk4ScreenT<true, true, F16, EPI> tl;
     tl.sc = a.sc;
     tl.frun = a.frun + (size_t)blockIdx.x * 1024;
     tl.first = t == 0;
@@ -1033,6 +1184,10 @@ __global__ __launch_bounds__(256) void k_trunk4sr(TrunkRunArgs args) {
 __global__ __launch_bounds__(256) void k_trunk4sr16(TrunkRunArgs args) {  // with the fp16 screen (`screen_f16`)
   (void)args;
   trunk4sr_body<true>();
+}
+__global__ __launch_bounds__(256) void k_trunk4sr16e(TrunkRunArgs args) {  // ... and the lean epilogue (`screen_epi`)
+  (void)args;
+  trunk4sr_body<true, true>();
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1051,7 +1206,7 @@ using StnPipeT = typename ScreenPipeSel<F16, StnScreenPipeF16, StnScreenPipe>::t
 // probe_rows (tests only): the image rows as [tile][64][128]
 // RUN: the run form (k_stn*_pair_sr) - frun = the 1024 running maxima of the run (LDS, -inf in front of the first tile;
 // first_pair: they are not to be read)
-template <int LAYER, bool POOL, bool RUN = false, bool F16 = false>
+template <int LAYER, bool POOL, bool RUN = false, bool F16 = false, bool EPI = false>
 __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scratch, StnPipeT<F16>& g,
                                                    const f32x4* __restrict__ wp3, const float* __restrict__ b3,
                                                    float* __restrict__ pm, int tile0, int valid2, const ScreenArgs& sc,
@@ -1083,7 +1238,7 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
     // the lane id is computed afresh behind the sweep (see Trunk4Screen::store: the sweep leaves no register for it)
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(ln));
     const f32x4* wf = wp3 + ((size_t)mb0 * 16) * 64 + (ln & 31);
-    screen_select_store<8, 128, false, LAYER, POOL, RUN, F16>(acc, wf, sc.nw, scratch + t * TP, x, sets,
+    screen_select_store<8, 128, false, LAYER, POOL, RUN, F16, EPI>(acc, wf, sc.nw, scratch + t * TP, x, sets,
                                                               pm + (size_t)(tile0 + t) * PMW, b3, mb0 * 32, true,
                                                               min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128, frun,
                                                               first_pair && t == 0, sa);
@@ -1098,7 +1253,7 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
 
 // POOL: the pooled replay (screen_pool_store) - k_stn3d_pair_sp / k_stnkd_pair_sp
 // (bid, tid): blockIdx.x and threadIdx.x of the one-pair kernels; the run form walks several pairs (RUN, frun, first_pair)
-template <bool POOL, bool RUN = false, bool F16 = false>
+template <bool POOL, bool RUN = false, bool F16 = false, bool EPI = false>
 __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* __restrict__ W1,
                                                   const float* __restrict__ b1, const f32x4* __restrict__ wp2,
                                                   const float* __restrict__ b2, const f32x4* __restrict__ wp3,
@@ -1134,22 +1289,24 @@ __device__ __forceinline__ void stn3d_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, a2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<1, POOL, RUN, F16>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
+  stn_conv3_screened<1, POOL, RUN, F16, EPI>(a2, a1, g3, wp3, b3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
-#define STN3D_PAIR_S_(NAME, POOL, F16)                                                                                        \
+#define STN3D_PAIR_S_(NAME, POOL, F16, EPI)                                                                                     \
   __global__ __launch_bounds__(256) void NAME(catre_points P, const float* __restrict__ W1, const float* __restrict__ b1, \
                                               const f32x4* __restrict__ wp2, const float* __restrict__ b2,                \
                                               const f32x4* __restrict__ wp3, const float* __restrict__ b3,                \
                                               float* __restrict__ pm, int B, int N, int M, ScreenArgs sc,                 \
                                               float* __restrict__ probe_rows) {                                           \
-    stn3d_pair_s_body<POOL, false, F16>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, probe_rows, blockIdx.x, threadIdx.x); \
+    stn3d_pair_s_body<POOL, false, F16, EPI>(P, W1, b1, wp2, b2, wp3, b3, pm, B, N, M, sc, EPI ? nullptr : probe_rows, blockIdx.x, \
+                                             threadIdx.x);                                                              \
   }
-STN3D_PAIR_S_(k_stn3d_pair_s, false, false)
-STN3D_PAIR_S_(k_stn3d_pair_sp, true, false)
-STN3D_PAIR_S_(k_stn3d_pair_sp16, true, true)
+STN3D_PAIR_S_(k_stn3d_pair_s, false, false, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp, true, false, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp16, true, true, false)
+STN3D_PAIR_S_(k_stn3d_pair_sp16e, true, true, true)  // `screen_epi`: no probe, probe_rows is not read
 #undef STN3D_PAIR_S_
 
-template <bool POOL, bool RUN = false, bool F16 = false>
+template <bool POOL, bool RUN = false, bool F16 = false, bool EPI = false>
 __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* __restrict__ trans3,
                                                   const float* __restrict__ Wc1, const float* __restrict__ bc1,
                                                   const f32x4* __restrict__ wpf1, const float* __restrict__ bf1,
@@ -1200,20 +1357,21 @@ __device__ __forceinline__ void stnkd_pair_s_body(catre_points P, const float* _
     store_tile_lds_pre<1, 4, true, false>(acc, f2, LD128, wave * 32, bv2, lane);
   }
   __syncthreads();
-  stn_conv3_screened<2, POOL, RUN, F16>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
+  stn_conv3_screened<2, POOL, RUN, F16, EPI>(f2, h1, g3, wpf3, bf3, pm, tile0, ti.valid, sc, probe_rows, wave, tid, lane, frun, first_pair);
 }
-#define STNKD_PAIR_S_(NAME, POOL, F16)                                                                                    \
+#define STNKD_PAIR_S_(NAME, POOL, F16, EPI)                                                                                 \
   __global__ __launch_bounds__(256) void NAME(                                                                        \
       catre_points P, const float* __restrict__ trans3, const float* __restrict__ Wc1, const float* __restrict__ bc1, \
       const f32x4* __restrict__ wpf1, const float* __restrict__ bf1, const f32x4* __restrict__ wpf2,                  \
       const float* __restrict__ bf2, const f32x4* __restrict__ wpf3, const float* __restrict__ bf3,                   \
       float* __restrict__ pm, int B, int N, int M, ScreenArgs sc, float* __restrict__ probe_rows) {                   \
-    stnkd_pair_s_body<POOL, false, F16>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc, probe_rows, \
-                            blockIdx.x, threadIdx.x);                                                                  \
+    stnkd_pair_s_body<POOL, false, F16, EPI>(P, trans3, Wc1, bc1, wpf1, bf1, wpf2, bf2, wpf3, bf3, pm, B, N, M, sc,    \
+                                             EPI ? nullptr : probe_rows, blockIdx.x, threadIdx.x);                     \
   }
-STNKD_PAIR_S_(k_stnkd_pair_s, false, false)
-STNKD_PAIR_S_(k_stnkd_pair_sp, true, false)
-STNKD_PAIR_S_(k_stnkd_pair_sp16, true, true)
+STNKD_PAIR_S_(k_stnkd_pair_s, false, false, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp, true, false, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp16, true, true, false)
+STNKD_PAIR_S_(k_stnkd_pair_sp16e, true, true, true)
 #undef STNKD_PAIR_S_
 
 // ------------------------------------------------------------------------------------------
@@ -1251,7 +1409,7 @@ struct Stn3dRunArgs {
   const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
 };
 
-template <bool F16>
+template <bool F16, bool EPI = false>
 __device__ __forceinline__ void stn3d_pair_sr_body() {
   __shared__ __attribute__((aligned(16))) float frun[1024];
   typedef const __attribute__((address_space(4))) Stn3dRunArgs* ArgPtr;
@@ -1268,7 +1426,7 @@ __device__ __forceinline__ void stn3d_pair_sr_body() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const Stn3dRunArgs a = *(const Stn3dRunArgs*)ap;
-    stn3d_pair_s_body<true, true, F16>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
+    stn3d_pair_s_body<true, true, F16, EPI>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
                                        ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane, frun,
                                        false);
     __syncthreads();  // the next pair's conv1 overwrites the candidate sets, its conv2 the image the other waves replay from
@@ -1281,6 +1439,10 @@ __global__ __launch_bounds__(256) void k_stn3d_pair_sr(Stn3dRunArgs args) {
 __global__ __launch_bounds__(256) void k_stn3d_pair_sr16(Stn3dRunArgs args) {
   (void)args;
   stn3d_pair_sr_body<true>();
+}
+__global__ __launch_bounds__(256) void k_stn3d_pair_sr16e(Stn3dRunArgs args) {  // `screen_epi`
+  (void)args;
+  stn3d_pair_sr_body<true, true>();
 }
 
 struct StnkdRunArgs {
@@ -1299,7 +1461,7 @@ struct StnkdRunArgs {
   const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
 };
 
-template <bool F16>
+template <bool F16, bool EPI = false>
 __device__ __forceinline__ void stnkd_pair_sr_body() {
   __shared__ __attribute__((aligned(16))) float frun[1024];
   typedef const __attribute__((address_space(4))) StnkdRunArgs* ArgPtr;
@@ -1316,7 +1478,7 @@ __device__ __forceinline__ void stnkd_pair_sr_body() {
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     asm volatile("" : "+s"(ap));
     const StnkdRunArgs a = *(const StnkdRunArgs*)ap;
-    stnkd_pair_s_body<true, true, F16>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N,
+    stnkd_pair_s_body<true, true, F16, EPI>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N,
                                        a.M, ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane,
                                        frun, false);
     __syncthreads();
@@ -1329,4 +1491,8 @@ __global__ __launch_bounds__(256) void k_stnkd_pair_sr(StnkdRunArgs args) {
 __global__ __launch_bounds__(256) void k_stnkd_pair_sr16(StnkdRunArgs args) {
   (void)args;
   stnkd_pair_sr_body<true>();
+}
+__global__ __launch_bounds__(256) void k_stnkd_pair_sr16e(StnkdRunArgs args) {  // `screen_epi`
+  (void)args;
+  stnkd_pair_sr_body<true, true>();
 }

@@ -307,7 +307,9 @@ def bump_param_epoch():
 
 
 FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7,
-            "screen_run": 8, "screen_f16": 9}
+            "screen_run": 8, "screen_f16": 9,
+            # no bit of the form word (ids 10 - 12 are the raw bits of the env-only STN arms): the epilogue of the `screen_f16` kernels
+            "screen_epi": 13}
 
 
 def form_switch(name, value=None):
@@ -334,7 +336,7 @@ def screen_run_rule(B, N, M, cus=256):
 KERNEL_FORMS = ("unsupported", "split_rs", "run_f16", "run", "screen_f16", "screen_pool", "screen", "pair", "wave4", "rs8",
                 "bf_pair", "bf", "train_split", "train_pair", "train_wave4", "train_rs1", "train_bf_pair", "train_bf")
 # bits of `switches`: ``FORM_IDS`` and the STN arms, which follow the environment only (CATRE_SCREEN_POOL_STN / _RUN_STN / _F16_STN)
-SWITCH_BITS = dict(FORM_IDS, screen_pool_stn=10, screen_run_stn=11, screen_f16_stn=12)
+SWITCH_BITS = dict({k: v for k, v in FORM_IDS.items() if v < 10}, screen_pool_stn=10, screen_run_stn=11, screen_f16_stn=12)
 STAGES = {"stn3d": 0, "stnkd": 1, "trunk": 2}
 MODES = {"fp32": 0, "split": 1, "bf16": 2}
 

@@ -351,6 +351,11 @@ int catre_profile_enable(int kernel_id, int max_records);
  * sum of squares past the fp32 range) cannot be scaled into fp16 and replay every point; likewise k_stn3d_pair_sp16 / _sr16
  * and k_stnkd_pair_sp16 / _sr16 (their own arm: CATRE_SCREEN_F16_STN = 0, read once per process, leaves the STN kernels on
  * the split-bf16 screen); it refines 7 and so 5; both probes follow it and return the fp16 screen value and its bound,
+ * 13 (`screen_epi`, CATRE_SCREEN_EPI = 0; ids 10 - 12 are the raw bits of the env-only STN arms and stay refused): the fp16-
+ * screen kernels of 9 with a leaner epilogue behind the sweep - each accumulator read once, the candidate mask built through
+ * the carry, the wave prefix on the DPP path, one scan loop - k_trunk4sr16e / k_trunk4sp16e and the four STN kernels of the
+ * same suffix; the same candidates and the same bits.  No form of its own (catre_form_decision does not read it); these
+ * kernels carry no probe code, a probe call takes the kernels of 9 (the trunk's: the one-tile kernel), default on,
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
  * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-9 on, 3 and 4 off -
  * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
@@ -389,13 +394,17 @@ int catre_form_decision(int stage, int mode, int save, int rows, int probe, int 
                         int run_len, int bf_pair_min, int* out);
 /* Experiment knobs of the instrumented library (id 0: start offset in cycles between the co-resident workgroups of the
  * STN kernels' first dispatch round, id 2: the screened kernels' counters of catre_debug_screen_counts on (1, default) / off
- * (0) - their atomics distort the phase stamps); CATRE_ERR_UNSUPPORTED in the product library. */
+ * (0) - their atomics distort the phase stamps, id 3: the screened epilogues' sub-phase stamps into the buffer of
+ * catre_debug_trunk_trace on (1) / off (0, default)); CATRE_ERR_UNSUPPORTED in the product library. */
 int catre_debug_knob(int id, int value);
 /* Wait for the recorded events, write per-launch durations (ms) and reset the record counter. */
 int catre_profile_collect(float* ms_out, int max_out, int* n_out);
 
 /* Debug aid: when non-NULL, every k_trunk workgroup writes 8 waves x 8 shader-clock stamps (u64) at its phase
- * boundaries into `device_buffer` ([tiles][8 waves][8]); NULL disables.  Process-global. */
+ * boundaries into `device_buffer` ([tiles][8 waves][8]); NULL disables.  Process-global.  After catre_debug_knob(3, 1)
+ * the pooled screened kernels also stamp their epilogue's sub-phases there (layer L at entry L << 22, rows 4 - 7 of a tile:
+ * profiles/trace_screen_epi.py); the buffer then holds at least 1 << 24 entries, and every call of this function turns
+ * those stamps off again. */
 int catre_debug_trunk_trace(void* device_buffer);
 /* Instrumented library only (CATRE_ERR_UNSUPPORTED in the product): the screened forms' counters since the last reset,
  * three rows of 64 (trunk conv4, stn.conv3, fstn.conv3) -
