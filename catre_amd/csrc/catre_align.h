@@ -31,6 +31,10 @@
 //   k_umeyama      the plain least-squares fit of the rows an optional byte mask keeps.
 //   k_align_draws  writes the evaluated draws out.
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
+#include "catre_pclf.h"  // the Philox draws of the depth augmentation
 
 #define ALIGN_MAX_ITER 128
 #define ALIGN_HB 32      // hypotheses counted per pass over the points

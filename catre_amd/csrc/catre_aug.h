@@ -4,6 +4,9 @@
 // (same generator consumption) and hands them in, so the kernels are deterministic functions that can be checked
 // against the reference's own outputs.
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 struct AugParams {
   float ratios[3];   // aug_3d_bbox: (ex, ey, ez)                       engine_utils.py:110-113

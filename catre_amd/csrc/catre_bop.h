@@ -26,6 +26,9 @@
 // Rounding: the fmas that are meant are written as fmas; elsewhere no product feeds a sum directly (a division or a root stands
 // between), except in bop_dist, which turns contraction off for its plain operators (see there).
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 constexpr int BOP_THREADS = 256;
 constexpr int BOP_WAVES = BOP_THREADS / 64;

@@ -25,6 +25,10 @@
 #include <stdint.h>
 
 #define TP 64  // points per tile
+// row pitches of the point-major fp32 LDS images: C + 4 floats (see above)
+#define LD64 68
+#define LD128 132
+#define LD256 260
 
 // Per-phase cycle stamps (profiles/trace_*.py) are compiled into the instrumented library only
 // (`make TRACE=1` -> libcatre_hip_trace.so); in the product library the stamp macros fold to nothing.
@@ -100,6 +104,23 @@ __device__ __forceinline__ float gelu_erf(float v) {
   return v * gelu_cdf(v);
 }
 
+__device__ __forceinline__ float group8_norm_gelu(float v, float gamma, float beta) {
+  // GroupNorm(32,256) on a [B,256] row: statistics over 8 consecutive channels = 8 consecutive lanes
+  float s = v;
+  s += __shfl_xor(s, 1);
+  s += __shfl_xor(s, 2);
+  s += __shfl_xor(s, 4);
+  const float mean = s * 0.125f;
+  const float d = v - mean;
+  float q = d * d;
+  q += __shfl_xor(q, 1);
+  q += __shfl_xor(q, 2);
+  q += __shfl_xor(q, 4);
+  const float rstd = 1.0f / sqrtf(q * 0.125f + 1e-5f);
+  const float sc = rstd * gamma;
+  return gelu_erf(fmaf(v, sc, beta - mean * sc));
+}
+
 // Two GELUs per instruction stream: the same operation sequence as gelu_erf (bit-identical results) written on
 // float2 (the packed-fp32 forms it once compiled to are disabled library-wide; the pairing still gives the
 // scheduler two independent chains).  Used where GELU is the bottleneck (rotation head: 2 x 2 x 256 x (N+M) evaluations per
@@ -167,6 +188,26 @@ __device__ __forceinline__ void gelu_affine4_lp(float v0, float v1, float v2, fl
   z[1] = gelu_erf_lp(fmaf(v1, sc[1], sh[1]));
   z[2] = gelu_erf_lp(fmaf(v2, sc[2], sh[2]));
   z[3] = gelu_erf_lp(fmaf(v3, sc[3], sh[3]));
+}
+
+// out[ch] = relu(W[ch][0..2] . (x,y,z) + b[ch]) for NCH consecutive channels starting at ch0 (wave-uniform)
+template <int NCH>
+__device__ __forceinline__ void conv3_relu_row(float x, float y, float z, const float* __restrict__ W,
+                                               const float* __restrict__ b, int ch0, float* out_row) {
+#pragma unroll
+  for (int c4 = 0; c4 < NCH / 4; ++c4) {
+    f32x4 v;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int ch = ch0 + c4 * 4 + q;
+      float t = b[ch];
+      t = fmaf(W[ch * 3 + 0], x, t);
+      t = fmaf(W[ch * 3 + 1], y, t);
+      t = fmaf(W[ch * 3 + 2], z, t);
+      v[q] = fmaxf(t, 0.f);
+    }
+    *reinterpret_cast<f32x4*>(out_row + ch0 + c4 * 4) = v;
+  }
 }
 
 // One K-sweep of a wave tile: MB x NB blocks of 32x32, K = 8*NKC.

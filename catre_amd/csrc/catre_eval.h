@@ -10,6 +10,9 @@
 //   k_eval_match_pose  one thread per (t, group, degree thr, shift thr):  compute_match_from_degree_cm (:715-757)
 // Three launches whatever the number of images.  All arithmetic is double on float32 inputs.
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 constexpr int EVAL_NROT = 20;   // y rotations of a symmetric prediction (test_utils.py:197)
 constexpr int EVAL_THREADS = 128;

@@ -6,6 +6,7 @@
 #include <cstdlib>
 
 #include "../../include/catre_hip.h"
+#include "catre_host.h"  // align_up (the plain C++ part)
 
 namespace catre_host {
 
@@ -217,7 +218,6 @@ inline bool form_decision(int stage, int mode, bool save, bool rows, bool probe,
 }
 
 // ---- packed weights ----------------------------------------------------------------------------
-inline size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
 struct PackLayout {
   size_t stn_c2, stn_c3, fstn_c1, fstn_c2, fstn_c3, c2, c3, c4, rot_l0[2], rot_l1[2], ts_w0t, ts_w1t, sumwp, total;

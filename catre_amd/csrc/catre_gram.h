@@ -17,6 +17,8 @@
 // are then those of the fp32 W0 on the rounded pointfeat, ~1e-4 relative from what the bf16 layer 0 computes).
 // Everything is fp32; sums of squares are always taken about a mean (tile mean, then cloud mean), never raw.
 #pragma once
+#include "catre_rot.h"
+#include "catre_bf16.h"
 
 // One workgroup per CLOUD (grid 2B): streams the cloud's pointfeat rows tile by tile (next tile's global loads in
 // flight under the current tile's MFMAs, two LDS buffers) and accumulates, about a fixed per-cloud shift c (the mean of

@@ -11,6 +11,8 @@
 //     per-tile partial sums merged in tile order - no atomics, so results are bit-identical from run to run and an object's
 //     result does not depend on the batch around it.
 // ------------------------------------------------------------------------------------------------
+#pragma once
+#include "catre_train.h"
 #define HA_TP 64      // rows per tile
 #define HA_MAXC 1024  // widest row
 

@@ -21,6 +21,8 @@
 //               earlier, pose and scale pass through bit for bit.  rmse and kept are reported regardless.
 // Nothing depends on the launch geometry or on the batch around an instance.  No floating-point atomics, no matrix form.
 #pragma once
+#include "catre_track.h"
+#include "catre_align.h"
 
 constexpr int ICP_FEW = CATRE_ICP_FEW, ICP_DEGENERATE = CATRE_ICP_DEGENERATE, ICP_NONFINITE = CATRE_ICP_NONFINITE;
 

@@ -9,6 +9,9 @@
 // The shipped form (l1, R only, key points) runs the loop it always ran, statement for statement, in a branch of its
 // own: its bits are pinned by tests/golden/loss_abi_shipped.npz.  Every other form takes the general loop below it.
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 typedef catre_loss_cfg2 LossCfg;  // include/catre_hip.h: catre_loss_cfg (first member `base`) + the PM form
 

@@ -10,6 +10,9 @@
 //   k_pcl_gather  per sample slot: pixel -> 3-D point; the slot -> candidate map is either the caller's
 //                 torch.randperm (reference-exact random stream) or a keyed Feistel permutation (no host sync)
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 #define PCL_CHUNK 4096
 #define PCL_NR 10  // radii tried by crop_ball_from_pts: r0 * 1.1^i, i = 0..9
@@ -369,3 +372,7 @@ __global__ __launch_bounds__(1024) void k_pcl_fps(const float* __restrict__ dept
     __syncthreads();
   }
 }
+
+
+// host side: the frame sizes the kernels above index in 32 bits (also the frame-batch ABI, catre_pclf_api.inc)
+inline bool pcl_frame_ok(int H, int W) { return H > 0 && W > 0 && (size_t)H * (size_t)W < ((size_t)1 << 30); }

@@ -15,6 +15,7 @@
 // The tables (frame_of, rank_of, label_of, cams, seeds) are validated on the host and staged by the entry points
 // (catre_pclf_api.inc); the kernels that read a frame index from device memory still refuse one outside [0, F).
 #pragma once
+#include "catre_pcl.h"
 
 // MODE 0: byte masks [I,H,W] (or none); MODE 1: label images [F,H,W] of LT + label_of [I]
 template <int MODE, typename LT>

@@ -1,5 +1,5 @@
 // C ABI of the frame-batched point-cloud preparation and the depth augmentation (kernels: catre_pclf.h, the
-// single-frame kernels and the workspace layout they share: catre_pcl.h and the pcl block of catre_kernels.hip;
+// single-frame kernels and the workspace layout they share: catre_pcl.h and catre_pcl_api.inc;
 // declarations: include/catre_hip.h)
 namespace {
 // head of the workspace: the per-instance and per-frame tables the entry points stage, then the single-frame layout

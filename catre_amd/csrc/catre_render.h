@@ -20,6 +20,11 @@
 // The projection is ONE device function (splat_project) for the splat and the visibility launch: same bits.  Every product,
 // quotient and sum in it is spelled with a rounding intrinsic so that nothing is contracted or reordered.
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
+#include "catre_pcl.h"
+#include "catre_track.h"
 
 constexpr int SPLAT_THREADS = 256;
 constexpr unsigned long long SPLAT_BG = ~0ull;

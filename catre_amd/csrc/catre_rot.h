@@ -10,6 +10,7 @@
 // k_rot_l1 is sized for TWO workgroups per CU: 256 threads, 64 accumulator VGPRs per layer, and exactly
 // 80 KiB of LDS (pointfeat tile 16 KiB + a0 image 64 KiB, both XOR-swizzled instead of padded).
 #pragma once
+#include "catre_fc.h"
 
 // (mean, M2) partials [rows][T][32][2] -> (mean, rstd) [rows][32][2]; one workgroup per row (row = object*2+head): the
 // row's partials are staged in LDS with coalesced loads, then 32 threads merge them in tile order (the merge is a serial

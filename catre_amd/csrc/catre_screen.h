@@ -84,6 +84,7 @@
 //   term for the tile's largest point).  infl as above with 2^-19 for the roundings of eps's own operations.
 //   An eps that overflows to +inf makes every point a candidate, as it must.
 #pragma once
+#include "catre_split.h"
 
 template <int K>
 struct ScreenBound {

@@ -18,6 +18,9 @@
 //     result is not needed before the pose update;
 //   * k_finish_update: the rot heads' tile sums (k_rot_finish) and the pose update in one launch.
 #pragma once
+#include "catre_gram.h"
+#include "catre_pose.h"
+#include "catre_bf16.h"
 
 #define SMALL_ROWS 16            // clouds (2B) up to which the latency path is taken
 #define SMALL_FOLD_ROWS 4        // clouds up to which the consumers of a pooled feature reduce the tile partials themselves

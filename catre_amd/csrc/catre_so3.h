@@ -1,5 +1,5 @@
 // catre_so3.h - a10: the four rotation parametrisations of get_rot_mat (core/catre/models/model_utils.py:28-40) and
-// their reverse-mode derivatives, one object per thread (included by catre_kernels.hip before the pose-update kernels).
+// their reverse-mode derivatives, one object per thread.  Device functions only: the kernels on them are in catre_pose.h.
 //
 //   CATRE_ROT_6D        [B,6]  rot6d_to_mat_batch          core/utils/rot_reps.py:34-55
 //   CATRE_ROT_QUAT      [B,4]  quat2mat_torch              core/utils/pose_utils.py:349-412   (w, x, y, z; eps = 0)
@@ -11,6 +11,9 @@
 // graph produces 0 * inf = NaN (lie_vec at exactly v = 0: sqrt'(0) under a zero mask; log_quat at v = 0: norm'(0)) the
 // finite masked-branch value is returned instead (the first-order branch's gradient / zero).
 #pragma once
+#include "catre_device.h"
+
+#include "../../include/catre_hip.h"
 
 __host__ __device__ inline int catre_rot_dim(int rot_type) {
   return rot_type == CATRE_ROT_QUAT ? 4 : (rot_type == CATRE_ROT_6D ? 6 : 3);
@@ -211,33 +214,4 @@ __device__ __forceinline__ void rot_param_to_mat_bwd(const float* r, int rot_typ
     case CATRE_ROT_LIE_VEC: lie_vec_to_mat_bwd(r, gR, g); break;
     default: rot6d_to_mat_bwd(r, gR, g);
   }
-}
-
-// get_rot_mat as a stand-alone launch: rot [B,d] -> R [B,3,3]; and its backward gR [B,3,3] -> g [B,d]
-__global__ void k_rot_to_mat(const float* __restrict__ rot, int rot_type, float* __restrict__ R, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const int d = catre_rot_dim(rot_type);
-  float r[6], m[9];
-#pragma unroll
-  for (int i = 0; i < 6; ++i) r[i] = i < d ? rot[(size_t)b * d + i] : 0.f;  // fixed trip count: r stays in registers
-  rot_param_to_mat(r, rot_type, m);
-#pragma unroll
-  for (int i = 0; i < 9; ++i) R[(size_t)b * 9 + i] = m[i];
-}
-
-__global__ void k_rot_to_mat_bwd(const float* __restrict__ rot, int rot_type, const float* __restrict__ gR,
-                                 float* __restrict__ g, int B) {
-  const int b = blockIdx.x * blockDim.x + threadIdx.x;
-  if (b >= B) return;
-  const int d = catre_rot_dim(rot_type);
-  float r[6], gm[9], go[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-  for (int i = 0; i < 6; ++i) r[i] = i < d ? rot[(size_t)b * d + i] : 0.f;
-#pragma unroll
-  for (int i = 0; i < 9; ++i) gm[i] = gR[(size_t)b * 9 + i];
-  rot_param_to_mat_bwd(r, rot_type, gm, go);
-#pragma unroll
-  for (int i = 0; i < 6; ++i)
-    if (i < d) g[(size_t)b * d + i] = go[i];
 }

@@ -1,7 +1,7 @@
 // catre_split.h - the "split" compute mode: fp32-accurate GEMMs on the bf16 matrix pipe for the three layers that
 // hold 98 % of the path's FLOPs (all MFMA layers of the two STNs, trunk conv3 128->512 and conv4 512->1024, rot-head
 // layers 0 64->256 and 1 256->256).
-// Included by catre_kernels.hip after catre_bf16.h.
+// split_bf8 and the split K-sweep pipe GemmPipeS are in catre_mma.h.
 //
 // Every fp32 operand x is written as x = hi + lo with hi = bf16(x), lo = bf16(x - hi): 16 bits of mantissa.  A product
 // is accumulated in fp32 as  a_hi*b_hi + a_hi*b_lo + a_lo*b_hi  - three v_mfma_f32_32x32x16_bf16 (96 cycles per K=16)
@@ -14,17 +14,7 @@
 // workgroup shapes of the fp32 kernels are kept.  Images and weight fragments use the bf16 chunk / k-slot layout of
 // catre_bf16.h; the lo pack follows the hi pack in the packed-weight buffer.
 #pragma once
-
-__device__ __forceinline__ void split_bf8(const float (&v)[8], u32x4& hi, u32x4& lo) {
-  float r[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    hi[i] = pack_bf2(v[2 * i], v[2 * i + 1]);
-    r[2 * i] = v[2 * i] - bf_lo(hi[i]);
-    r[2 * i + 1] = v[2 * i + 1] - bf_hi(hi[i]);
-  }
-  lo = pack_bf8(r);
-}
+#include "catre_bf16.h"
 
 // weights -> hi and lo bf16 fragments in k-slot order: dst[0 .. rows*K) = hi, dst[rows*K .. 2 rows*K) = lo
 __global__ void k_pack_frag_split(const float* __restrict__ src, int ld, int coloff, int rows, int K,
@@ -41,68 +31,6 @@ __global__ void k_pack_frag_split(const float* __restrict__ src, int ld, int col
   dst[(size_t)rows * K + idx] = __builtin_bit_cast(unsigned short, (__bf16)(w - (float)h));
 }
 
-// K-sweep with split operands.  wp: hi fragments of the wave's first m-block, the lo fragments sit `lo_off` u32x4
-// further; xh / xl: hi and lo images (row of point 0 of the wave tile).  Per K=16 step and (mb, nb): 3 MFMAs.
-template <int MB, int NB, bool SWAP, int CP, int PFD>
-struct GemmPipeS {
-  static constexpr int NKC = CP / 2;
-  static_assert(PFD >= 1 && PFD <= NKC, "prefetch depth");
-  static constexpr int RA = PFD + 1;
-  u32x4 ah[RA][MB], al[RA][MB], bh[2][NB], bl[2][NB];
-  const u32x4* wp;
-  int wp_mb, lo_off;
-
-  __device__ __forceinline__ void issue_a(int kc) {
-#pragma unroll
-    for (int mb = 0; mb < MB; ++mb) {
-      ah[kc % RA][mb] = wp[mb * wp_mb + kc * 64];
-      al[kc % RA][mb] = wp[lo_off + mb * wp_mb + kc * 64];
-    }
-  }
-  __device__ __forceinline__ void prefetch(const u32x4* __restrict__ wp_, int wp_mb_, int lo_off_) {
-    wp = wp_;
-    wp_mb = wp_mb_;
-    lo_off = lo_off_;
-#pragma unroll
-    for (int d = 0; d < PFD; ++d) issue_a(d);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-  __device__ __forceinline__ void run(f32x16 (&acc)[MB][NB], const u32x4* xh, const u32x4* xl, int lane) {
-    const int n = lane & 31, h = lane >> 5, key = bf_key<CP>(n);
-    const u32x4* rh = xh + n * CP;
-    const u32x4* rl = xl + n * CP;
-    auto issue_b = [&](int kc) {
-#pragma unroll
-      for (int nb = 0; nb < NB; ++nb) {
-        bh[kc & 1][nb] = rh[nb * 32 * CP + ((2 * kc + h) ^ key)];
-        bl[kc & 1][nb] = rl[nb * 32 * CP + ((2 * kc + h) ^ key)];
-      }
-    };
-    issue_b(0);
-#pragma unroll
-    for (int kc = 0; kc < NKC; ++kc) {
-      if (kc + PFD < NKC) issue_a(kc + PFD);
-      if (kc + 1 < NKC) issue_b(kc + 1);
-      __builtin_amdgcn_sched_barrier(0);
-      const int ca = kc % RA, cb = kc & 1;
-#pragma unroll
-      for (int mb = 0; mb < MB; ++mb)
-#pragma unroll
-        for (int nb = 0; nb < NB; ++nb) {
-          if (SWAP) {
-            acc[mb][nb] = mfma_bf(bh[cb][nb], al[ca][mb], acc[mb][nb]);
-            acc[mb][nb] = mfma_bf(bl[cb][nb], ah[ca][mb], acc[mb][nb]);
-            acc[mb][nb] = mfma_bf(bh[cb][nb], ah[ca][mb], acc[mb][nb]);
-          } else {
-            acc[mb][nb] = mfma_bf(al[ca][mb], bh[cb][nb], acc[mb][nb]);
-            acc[mb][nb] = mfma_bf(ah[ca][mb], bl[cb][nb], acc[mb][nb]);
-            acc[mb][nb] = mfma_bf(ah[ca][mb], bh[cb][nb], acc[mb][nb]);
-          }
-        }
-      __builtin_amdgcn_sched_barrier(0);
-    }
-  }
-};
 
 // "normal"-orientation epilogue of an fp32 layer into split images: act(acc + bias) -> hi chunk + lo chunk
 template <int MB, int NB, bool RELU, int CP>
@@ -714,3 +642,32 @@ __global__ __launch_bounds__(256, 2) void k_rot_l1_split(const float* __restrict
   }
 #undef ROTS_STAMP
 }
+
+// every bf16 (or hi + lo split) fragment pack of a weight image in ONE launch (k_pack_frag_multi's job table; the
+// per-element arithmetic is k_pack_frag_bf's / k_pack_frag_split's): a training step re-packs the image after every
+// optimizer step, and twelve 3-us launches sat on the critical path of each autocast / split iteration
+// OT = OpF16: the fp16 packs of the same matrices (k_pack_frag_hf_multi; no split kind)
+template <bool SPLIT, class OT = OpBf16>
+__device__ __forceinline__ void pack_frag_lp_body(const PackJobs& J) {
+  static_assert(!SPLIT || !is_f16_op<OT>(), "the split packs are bf16 pairs");
+  const int gi = blockIdx.x * blockDim.x + threadIdx.x;
+  if (gi >= J.end[J.n - 1]) return;
+  int j = 0;
+  while (gi >= J.end[j]) ++j;
+  const int base = j ? J.end[j - 1] : 0, idx = gi - base, total = J.end[j] - base;  // total = rows * K
+  const int K = J.K[j];
+  const int e = idx & 7, lane = (idx >> 3) & 63, rest = idx >> 9;
+  const int nkc = K / 16;
+  const int kc = rest % nkc, mb = rest / nkc;
+  const int row = mb * 32 + (lane & 31), col = kc * 16 + 8 * (e >> 2) + 4 * (lane >> 5) + (e & 3);
+  const float w = J.src[j][(size_t)row * J.ld[j] + J.coloff[j] + col];
+  unsigned short* dst = reinterpret_cast<unsigned short*>(J.dst[j]);
+  const typename OT::T h = (typename OT::T)w;
+  dst[idx] = __builtin_bit_cast(unsigned short, h);
+  if constexpr (SPLIT) dst[(size_t)total + idx] = __builtin_bit_cast(unsigned short, (__bf16)(w - (float)h));
+}
+template <bool SPLIT>
+__global__ void k_pack_frag_lp_multi(PackJobs J) {
+  pack_frag_lp_body<SPLIT>(J);
+}
+__global__ void k_pack_frag_hf_multi(PackJobs J) { pack_frag_lp_body<false, OpF16>(J); }

@@ -16,6 +16,8 @@
 // same bits alone and inside any batch.  No floating-point atomics.
 // k_track_gate one thread per instance: status bits, carried pose / scale, age.
 #pragma once
+#include "catre_device.h"
+#include "catre_host.h"
 
 constexpr int NN_THREADS = 256;  // src points per workgroup
 constexpr int NN_CHUNK = 1024;   // dst points staged in LDS at a time (16 KiB as float4)
@@ -176,3 +178,18 @@ __global__ void k_track_gate(const float* __restrict__ pose_new, const float* __
   status[i] = st;
   age[i] = st ? age[i] + 1 : 0;
 }
+
+
+// ---- host side: grid and workspace sizing of catre_nn_stats, shared by its ABI (catre_track_api.inc) and the ICP ABI
+// (catre_icp_api.inc), which runs the same neighbour search
+namespace {
+inline int nn_tiles(int n_src) { return (n_src + NN_THREADS - 1) / NN_THREADS; }
+// one launch covers every (instance, tile): I * tiles workgroups of NN_THREADS threads, kept below 2^32 threads in all
+constexpr size_t NN_MAX_GROUPS = ((size_t)1 << 32) / NN_THREADS - 1;
+inline bool nn_dims_ok(int I, int n_src, int n_dst) {
+  return I > 0 && n_src > 0 && n_dst > 0 && (size_t)n_src * 3 < ((size_t)1 << 31) && (size_t)n_dst * 3 < ((size_t)1 << 31) &&
+         (size_t)I * nn_tiles(n_src) <= NN_MAX_GROUPS;
+}
+// [I * tiles] double partial sums, then [I * tiles] int32 partial counts
+inline size_t nn_ws_bytes(int I, int n_src) { return catre_host::align_up((size_t)I * nn_tiles(n_src) * 12, 16); }
+}  // namespace

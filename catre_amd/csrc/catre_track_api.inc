@@ -1,15 +1,4 @@
-// C ABI of the tracking kernels (kernels: catre_track.h; declarations: include/catre_hip.h)
-namespace {
-inline int nn_tiles(int n_src) { return (n_src + NN_THREADS - 1) / NN_THREADS; }
-// one launch covers every (instance, tile): I * tiles workgroups of NN_THREADS threads, kept below 2^32 threads in all
-constexpr size_t NN_MAX_GROUPS = ((size_t)1 << 32) / NN_THREADS - 1;
-inline bool nn_dims_ok(int I, int n_src, int n_dst) {
-  return I > 0 && n_src > 0 && n_dst > 0 && (size_t)n_src * 3 < ((size_t)1 << 31) && (size_t)n_dst * 3 < ((size_t)1 << 31) &&
-         (size_t)I * nn_tiles(n_src) <= NN_MAX_GROUPS;
-}
-// [I * tiles] double partial sums, then [I * tiles] int32 partial counts
-inline size_t nn_ws_bytes(int I, int n_src) { return align_up((size_t)I * nn_tiles(n_src) * 12, 16); }
-}  // namespace
+// C ABI of the tracking kernels (kernels and the nn_* sizing helpers: catre_track.h; declarations: include/catre_hip.h)
 
 size_t catre_nn_stats_workspace_bytes(int I, int n_src, int n_dst) {
   return nn_dims_ok(I, n_src, n_dst) ? nn_ws_bytes(I, n_src) : 0;

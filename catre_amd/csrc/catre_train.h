@@ -13,6 +13,9 @@
 //               per-cloud 3x3 / 64x64 transforms, GroupNorm over points / rows, GELU, conv_p weighted sum,
 //               rot6d + pose-update backward.
 #pragma once
+#include "catre_device.h"
+#include "catre_mma.h"
+#include "catre_so3.h"
 
 // ------------------------------------------------------------------------------------------------
 // weight packing for gemm_rows: logical matrix Wl[J][K]; transpose=1 reads Wl[j][k] = src[k*ld + j]
@@ -1089,7 +1092,7 @@ __global__ __launch_bounds__(256, 2) void k_gemm_tn_lp(const float* __restrict__
 
 // ------------------------------------------------------------------------------------------------
 // The whole backward of a linear layer on FEW rows (R < 2048: the STNs' FC tails, the ts head, the rotation heads' global
-// halves - rows are clouds or objects) as ONE launch, in the latency form of k_linear (catre_kernels.hip): a workgroup per
+// halves - rows are clouds or objects) as ONE launch, in the latency form of k_linear (catre_fc.h): a workgroup per
 // 32 x 32 output block, its 8 waves split the contraction in interleaved 8-wide chunks with up to 8 chunks in flight per
 // wave, operands straight from L2, partial blocks summed through LDS in wave order (deterministic, no split buffers, no
 // merge launch).  dv = dY .* (YM > 0):
@@ -4243,100 +4246,4 @@ __global__ void k_sum_acc(const float* __restrict__ src, int n, float* __restric
   if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
   __syncthreads();
   if (threadIdx.x == 0) dst[0] = (accumulate ? dst[0] : 0.f) + ((red[0] + red[1]) + (red[2] + red[3]));
-}
-
-// ------------------------------------------------------------------------------------------------
-// f4: fused multi-tensor Ranger step (RAdam + Lookahead + gradient centralization) with the train loop's
-// grad nan_to_num folded in.  Replaces the per-tensor Python loop of lib/torch_utils/solver/ranger.py:102-202
-// (~70 tensors x ~15 torch ops, K times per data batch) and core/catre/engine/engine.py:351-353.
-// The host computes the scalar step sizes; the device table carries one RangerTensor per parameter.
-// ------------------------------------------------------------------------------------------------
-struct RangerTensor {
-  float* p;
-  const float* g;
-  float* m;      // exp_avg
-  float* v;      // exp_avg_sq
-  float* slow;   // lookahead slow weights
-  int numel;
-  int row_len;   // > 0: centralize the gradient over rows of this length (dims 1.. of a conv / fc weight)
-  int row_off;   // first slot of this tensor in the row-mean buffer
-  float lr_step; // step_size * lr
-  float wd_lr;   // weight_decay * lr
-  int adaptive;  // N_sma > threshold: divide by sqrt(v) + eps
-  int lookahead; // step % k == 0: merge into the slow weights
-  int pad;
-};
-static_assert(sizeof(RangerTensor) == 72, "host packs this struct with the same layout");
-
-__device__ __forceinline__ float ranger_clean(float g, int clean, float lim) {
-  // torch.nan_to_num(g, nan=0, posinf=lim, neginf=-lim) (engine.py:351-353): finite values pass unchanged
-  if (!clean) return g;
-  if (g != g) return 0.f;
-  return g == INFINITY ? lim : (g == -INFINITY ? -lim : g);
-}
-
-// one wave per (tensor, row): mean of the (cleaned) gradient row
-__global__ __launch_bounds__(64) void k_ranger_rowmean(const RangerTensor* __restrict__ T, const int* __restrict__ row_tensor,
-                                                       float* __restrict__ rowmean, int clean, float lim) {
-  const int row = blockIdx.x;
-  const RangerTensor t = T[row_tensor[row]];
-  const int r = row - t.row_off;
-  const float* g = t.g + (size_t)r * t.row_len;
-  float s = 0.f;
-  int i = threadIdx.x;
-  for (; i + 192 < t.row_len; i += 256) {  // four loads requested together, added in the loop's order (same bits)
-    const float a = g[i], b = g[i + 64], c = g[i + 128], d = g[i + 192];
-    s += ranger_clean(a, clean, lim);
-    s += ranger_clean(b, clean, lim);
-    s += ranger_clean(c, clean, lim);
-    s += ranger_clean(d, clean, lim);
-  }
-  for (; i < t.row_len; i += 64) s += ranger_clean(g[i], clean, lim);
-  s = wave_sum(s);
-  if (threadIdx.x == 0) rowmean[row] = s / (float)t.row_len;
-}
-
-#define RANGER_CHUNK 4096
-__global__ __launch_bounds__(256) void k_ranger_update(const RangerTensor* __restrict__ T, const int2* __restrict__ chunks,
-                                                       const float* __restrict__ rowmean, float beta1, float omb1,
-                                                       float beta2, float omb2, float eps, float alpha, int clean,
-                                                       float lim) {
-  const int2 c = chunks[blockIdx.x];
-  const RangerTensor t = T[c.x];
-  const int end = min(t.numel, c.y + RANGER_CHUNK);
-  // four elements per thread and trip, every load of the trip requested before the first store (the tensors may alias as far
-  // as the compiler knows: as a plain loop each element waited for the previous one's stores - 16 dependent round trips)
-  for (int i0 = c.y + threadIdx.x; i0 < end; i0 += 1024) {
-    float g[4], v[4], m[4], p[4], sl[4], rm[4];
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = min(i0 + 256 * u, end - 1);
-      g[u] = t.g[i], v[u] = t.v[i], m[u] = t.m[i], p[u] = t.p[i];
-      sl[u] = t.lookahead ? t.slow[i] : 0.f;
-      rm[u] = t.row_len > 0 ? rowmean[t.row_off + i / t.row_len] : 0.f;
-    }
-    __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-    for (int u = 0; u < 4; ++u) {
-      const int i = i0 + 256 * u;
-      if (i < end) {
-        float gg = ranger_clean(g[u], clean, lim);
-        if (t.row_len > 0) gg -= rm[u];
-        // omb = fp32(1 - beta) formed in double on the host like the reference's `1 - beta2` (1.f - 0.999f is off by 4.7e-5)
-        const float vv = v[u] * beta2 + omb2 * gg * gg;
-        const float mm = m[u] * beta1 + omb1 * gg;
-        t.v[i] = vv;
-        t.m[i] = mm;
-        float pp = p[u];
-        if (t.wd_lr != 0.f) pp -= t.wd_lr * pp;
-        pp -= t.adaptive ? t.lr_step * (mm / (sqrtf(vv) + eps)) : t.lr_step * mm;
-        if (t.lookahead) {
-          const float s = sl[u] + alpha * (pp - sl[u]);
-          t.slow[i] = s;
-          pp = s;
-        }
-        t.p[i] = pp;
-      }
-    }
-  }
 }

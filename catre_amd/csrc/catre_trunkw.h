@@ -13,6 +13,8 @@
 // [0, D) when conv4's first D rows are the same.  The partial-max rows keep the 1088 pitch ([conv max | 64 pointfeat max]
 // at column 1024); k_reduce_pm_w gathers them into gfeat [C, D + 64].
 // ------------------------------------------------------------------------------------------
+#pragma once
+#include "catre_enc.h"
 template <int MB, int NB>
 __global__ __launch_bounds__(512) void k_trunkw(catre_points P, const float* __restrict__ trans3,
                                                 const float* __restrict__ trans64, const float* __restrict__ Wc1,

@@ -57,8 +57,9 @@ OBJDUMP = "/opt/rocm/lib/llvm/bin/llvm-objdump"
 
 
 def disassemble(lib_path):
-    """gfx950 code object of ``lib_path`` -> {kernel symbol: [instruction mnemonics]} (llvm-objdump of the offload bundle,
-    extracted into a temporary directory).  Used by the ISA lint of tests/test_resources.py."""
+    """gfx950 code objects of ``lib_path`` (one per translation unit) -> {kernel symbol: [instruction mnemonics]}, merged
+    (llvm-objdump of the offload bundles, extracted into a temporary directory).  A symbol defined in two code objects is
+    an error: a kernel header was compiled into two units.  Used by the ISA lint of tests/test_resources.py."""
     import shutil
     import tempfile
 
@@ -67,20 +68,27 @@ def disassemble(lib_path):
         so = os.path.join(d, "lib.so")
         shutil.copy(lib_path, so)
         subprocess.run([OBJDUMP, "--offloading", so], check=True, capture_output=True, cwd=d)
-        co = [f for f in os.listdir(d) if "gfx950" in f]
-        assert len(co) == 1, os.listdir(d)
-        text = subprocess.run([OBJDUMP, "-d", os.path.join(d, co[0])], check=True, capture_output=True, text=True).stdout
+        co = sorted(f for f in os.listdir(d) if "gfx950" in f)
+        assert co, os.listdir(d)
+        texts = [subprocess.run([OBJDUMP, "-d", os.path.join(d, f)], check=True, capture_output=True, text=True).stdout
+                 for f in co]
     finally:
         shutil.rmtree(d, ignore_errors=True)
-    out, cur = {}, None
-    for ln in text.splitlines():
-        m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)
-        if m:
-            cur = out.setdefault(m.group(1), [])
-            continue
-        m = re.match(r"^\s+([a-z_0-9]+)", ln)
-        if m and cur is not None:
-            cur.append(m.group(1))
+    out = {}
+    for text in texts:
+        unit, cur = {}, None
+        for ln in text.splitlines():
+            m = re.match(r"^[0-9a-f]+ <(\S+)>:", ln)
+            if m:
+                cur = unit.setdefault(m.group(1), [])
+                continue
+            m = re.match(r"^\s+([a-z_0-9]+)", ln)
+            if m and cur is not None:
+                cur.append(m.group(1))
+        twice = sorted(set(unit) & set(out))
+        if twice:
+            raise RuntimeError(f"{len(twice)} symbols are defined in two code objects of {lib_path}: {twice[:5]}")
+        out.update(unit)
     return out
 
 
