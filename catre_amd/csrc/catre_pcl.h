@@ -3,12 +3,16 @@
 // (lib/pysixd/misc.py:360-378), keeps the pixels of the instance mask with depth > 0
 // (core/utils/cat_data_utils.py:209-226), crops a ball around the pose centre whose radius grows x1.1 until it
 // holds >= 10 points (:289-311) and samples NUM_PCL of them (:313-320) - all on the CPU, instance by instance.
-// Here: all instances of an image in four launches.
+// Here: all instances of an image, or of a whole data batch, in four launches.
 //   k_pcl_count   per (instance, 4096-pixel chunk): how many valid pixels fall into each of the 10 candidate radii
 //   k_pcl_pick    per instance: choose the radius like the reference's loop, exclusive scan of the chunk counts
 //   k_pcl_compact per (instance, chunk): ordered (row-major, = torch.nonzero order) list of candidate pixels
 //   k_pcl_gather  per sample slot: pixel -> 3-D point; the slot -> candidate map is either the caller's
 //                 torch.randperm (reference-exact random stream) or a keyed Feistel permutation (no host sync)
+//   k_pcl_fps     per instance: INPUT.FPS_SAMPLE, the farthest-point order of the candidate list
+// Every body but k_pcl_pick is a template on a frame source, which says where an instance's depth map, camera, seed and
+// permutation key come from: PclOneFrame (catre_pcl_*: one image, everything by value) or PclFrameTable (catre_pclf_*:
+// a frame per instance, read from device tables).  One body, so a frame inside a batch gives the bits it gives alone.
 #pragma once
 #include "catre_device.h"
 
@@ -72,19 +76,67 @@ __device__ __forceinline__ int pcl_bin(const float* __restrict__ depth, const un
   return b;
 }
 
-__global__ __launch_bounds__(256) void k_pcl_count(const float* __restrict__ depth,
-                                                   const unsigned char* __restrict__ masks, const float* __restrict__ poses,
-                                                   const float* __restrict__ scales, PclCam cam, float ratio, int use_ball,
-                                                   int H, int W, int nchunks, int* __restrict__ bins /*[I][nchunks][12]*/) {
+// Frame sources.  frame(inst) indexes the depth maps [F][H*W] (and the label images); frames() = F; key(inst) keys the
+// device permutation together with seed(frame).
+// One image: camera and seed by value, no device table and no copy, so the catre_pcl_* launches can be captured.
+struct PclOneFrame {
+  PclCam cam_;
+  unsigned long long seed_;
+  __device__ __forceinline__ int frame(int) const { return 0; }
+  __device__ __forceinline__ int frames() const { return 1; }
+  __device__ __forceinline__ PclCam cam(int) const { return cam_; }
+  __device__ __forceinline__ unsigned long long seed(int) const { return seed_; }
+  __device__ __forceinline__ unsigned key(int inst) const { return (unsigned)inst; }
+};
+// A data batch: instance i reads frame frame_of[i] with the camera cams[frame] and the seed seeds[frame]; the key is the
+// rank of the instance within its frame, so a frame gets the cloud it gets alone whatever else is in the batch.  The
+// tables are validated on the host and staged by the entry points (catre_pclf_api.inc).
+struct PclFrameTable {
+  const int* frame_of;
+  const int* rank_of;
+  const PclCam* cams;
+  const unsigned long long* seeds;
+  int F;
+  __device__ __forceinline__ int frame(int inst) const { return frame_of[inst]; }
+  __device__ __forceinline__ int frames() const { return F; }
+  __device__ __forceinline__ PclCam cam(int frame) const { return cams[frame]; }
+  __device__ __forceinline__ unsigned long long seed(int frame) const { return seeds[frame]; }
+  __device__ __forceinline__ unsigned key(int inst) const { return (unsigned)rank_of[inst]; }
+};
+
+// pixel membership.  MODE 0: byte masks [I,H,W] (or none); MODE 1: label images [F,H,W] of LT + label_of [I], the pixels
+// where labels[frame][pix] == label_of[inst]
+template <int MODE, typename LT>
+__device__ __forceinline__ int pcl_bin_of(const float* __restrict__ depth_f, const unsigned char* __restrict__ mask_i,
+                                          const LT* __restrict__ labels_f, int label, int pix, int W, const PclCam& cam,
+                                          const float* centre, const float (&r)[PCL_NR], int use_ball) {
+  if (MODE == 1) {
+    if ((int)labels_f[pix] != label) return -1;
+    return pcl_bin(depth_f, nullptr, pix, W, cam, centre, r, use_ball);
+  }
+  return pcl_bin(depth_f, mask_i, pix, W, cam, centre, r, use_ball);
+}
+
+template <class SRC, int MODE, typename LT>
+__global__ __launch_bounds__(256) void k_pcl_count(SRC src, const float* __restrict__ depth,
+                                                   const unsigned char* __restrict__ masks, const LT* __restrict__ labels,
+                                                   const int* __restrict__ label_of, const float* __restrict__ poses,
+                                                   const float* __restrict__ scales, float ratio, int use_ball, int H, int W,
+                                                   int nchunks, int* __restrict__ bins /*[I][nchunks][12]*/) {
   __shared__ int cnt[12];
   const int inst = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x;
   if (tid < 12) cnt[tid] = 0;
   __syncthreads();
+  const int HW = H * W, frame = src.frame(inst);
+  const PclCam cam = src.cam(frame);
+  const float* depth_f = depth + (size_t)frame * HW;
+  const unsigned char* m = (MODE == 0 && masks) ? masks + (size_t)inst * HW : nullptr;
+  const LT* lab_f = MODE == 1 ? labels + (size_t)frame * HW : nullptr;
+  const int label = MODE == 1 ? label_of[inst] : 0;
   float r[PCL_NR];
   pcl_radii(poses + inst * 12, scales + inst * 3, ratio, r);
   const float centre[3] = {poses[inst * 12 + 3], poses[inst * 12 + 7], poses[inst * 12 + 11]};
-  const unsigned char* m = masks ? masks + (size_t)inst * H * W : nullptr;
-  const int p0 = chunk * PCL_CHUNK + tid * 16, HW = H * W;
+  const int p0 = chunk * PCL_CHUNK + tid * 16;
   int local[PCL_NR + 1];
 #pragma unroll
   for (int i = 0; i <= PCL_NR; ++i) local[i] = 0;
@@ -92,7 +144,7 @@ __global__ __launch_bounds__(256) void k_pcl_count(const float* __restrict__ dep
   for (int k = 0; k < 16; ++k) {
     const int pix = p0 + k;
     if (pix < HW) {
-      const int b = pcl_bin(depth, m, pix, W, cam, centre, r, use_ball);
+      const int b = pcl_bin_of<MODE, LT>(depth_f, m, lab_f, label, pix, W, cam, centre, r, use_ball);
 #pragma unroll
       for (int i = 0; i <= PCL_NR; ++i) local[i] += (b == i);
     }
@@ -168,26 +220,33 @@ __global__ __launch_bounds__(256) void k_pcl_pick(const int* __restrict__ bins, 
   }
 }
 
-__global__ __launch_bounds__(256) void k_pcl_compact(const float* __restrict__ depth,
+template <class SRC, int MODE, typename LT>
+__global__ __launch_bounds__(256) void k_pcl_compact(SRC src, const float* __restrict__ depth,
                                                      const unsigned char* __restrict__ masks,
+                                                     const LT* __restrict__ labels, const int* __restrict__ label_of,
                                                      const float* __restrict__ poses, const float* __restrict__ scales,
-                                                     PclCam cam, float ratio, int use_ball, int H, int W, int nchunks,
+                                                     float ratio, int use_ball, int H, int W, int nchunks,
                                                      const int* __restrict__ choose, const int* __restrict__ offsets,
                                                      int* __restrict__ cand /*[I][H*W]*/) {
   __shared__ int wsum[4];
   const int inst = blockIdx.y, chunk = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int HW = H * W, frame = src.frame(inst);
+  const PclCam cam = src.cam(frame);
+  const float* depth_f = depth + (size_t)frame * HW;
+  const unsigned char* m = (MODE == 0 && masks) ? masks + (size_t)inst * HW : nullptr;
+  const LT* lab_f = MODE == 1 ? labels + (size_t)frame * HW : nullptr;
+  const int label = MODE == 1 ? label_of[inst] : 0;
   float r[PCL_NR];
   pcl_radii(poses + inst * 12, scales + inst * 3, ratio, r);
   const float centre[3] = {poses[inst * 12 + 3], poses[inst * 12 + 7], poses[inst * 12 + 11]};
-  const unsigned char* m = masks ? masks + (size_t)inst * H * W : nullptr;
   const int k = choose[inst];
-  const int p0 = chunk * PCL_CHUNK + tid * 16, HW = H * W;
+  const int p0 = chunk * PCL_CHUNK + tid * 16;
   unsigned keep = 0;
 #pragma unroll 4
   for (int j = 0; j < 16; ++j) {
     const int pix = p0 + j;
     if (pix < HW) {
-      const int b = pcl_bin(depth, m, pix, W, cam, centre, r, use_ball);
+      const int b = pcl_bin_of<MODE, LT>(depth_f, m, lab_f, label, pix, W, cam, centre, r, use_ball);
       if (b >= 0 && b <= k) keep |= 1u << j;
     }
   }
@@ -240,22 +299,36 @@ __device__ __forceinline__ unsigned pcl_perm(unsigned i, unsigned L, unsigned lo
   return x;
 }
 
-__global__ __launch_bounds__(256) void k_pcl_gather(const float* __restrict__ depth, PclCam cam, int H, int W,
+// candidate count of an instance as the sampling kernels may trust it: the workspace is the caller's memory, so a count
+// or a frame index that candidates() did not write there (a workspace used out of order) selects nothing instead of
+// reading outside the depth maps
+__device__ __forceinline__ int pcl_count_ok(int cnt, int frame, int F, int HW) {
+  return ((unsigned)frame < (unsigned)F && cnt > 0 && cnt <= HW) ? cnt : 0;
+}
+
+template <class SRC>
+__global__ __launch_bounds__(256) void k_pcl_gather(SRC src, const float* __restrict__ depth, int H, int W,
                                                     const int* __restrict__ cand, const int* __restrict__ total,
-                                                    const long long* __restrict__ sample /*[I][N] or null*/,
-                                                    unsigned long long seed, int N, float* __restrict__ pcl_out,
-                                                    int* __restrict__ pix_out) {
+                                                    const long long* __restrict__ sample /*[I][N] or null*/, int N,
+                                                    float* __restrict__ pcl_out, int* __restrict__ pix_out) {
   const int inst = blockIdx.y, i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= N) return;
-  const int cnt = total[inst];
+  const int HW = H * W, frame = src.frame(inst);
+  const int cnt = pcl_count_ok(total[inst], frame, src.frames(), HW);
   float x = 0.f, y = 0.f, z = 0.f;
   int pix = -1;
   if (cnt > 0) {
     unsigned L = (unsigned)cnt;  // `while len(idx) < num_points: idx = cat([idx, idx])` -> idx tiled to length L
     while (L < (unsigned)N) L <<= 1;
-    const unsigned j = sample ? (unsigned)sample[(size_t)inst * N + i] : pcl_perm((unsigned)i, L, seed, (unsigned)inst);
-    pix = cand[(size_t)inst * H * W + (j % (unsigned)cnt)];
-    pcl_point(depth, pix, W, cam, x, y, z);
+    const unsigned j =
+        sample ? (unsigned)sample[(size_t)inst * N + i] : pcl_perm((unsigned)i, L, src.seed(frame), src.key(inst));
+    pix = cand[(size_t)inst * HW + (j % (unsigned)cnt)];
+    if ((unsigned)pix < (unsigned)HW) {
+      const PclCam cam = src.cam(frame);
+      pcl_point(depth + (size_t)frame * HW, pix, W, cam, x, y, z);
+    } else {
+      pix = -1;
+    }
   }
   float* o = pcl_out + ((size_t)inst * N + i) * 3;
   o[0] = x;
@@ -277,7 +350,8 @@ __device__ __forceinline__ float pcl_pdist(float ax, float ay, float az, float b
   return sqrtf(__fadd_rn(__fadd_rn(__fmul_rn(dx, dx), __fmul_rn(dy, dy)), __fmul_rn(dz, dz)));
 }
 
-__global__ __launch_bounds__(1024) void k_pcl_fps(const float* __restrict__ depth, PclCam cam, int H, int W,
+template <class SRC>
+__global__ __launch_bounds__(1024) void k_pcl_fps(SRC src, const float* __restrict__ depth, int H, int W,
                                                   const int* __restrict__ cand, const int* __restrict__ total, int N,
                                                   float* __restrict__ scratch, int Lcap,
                                                   long long* __restrict__ sample_out) {
@@ -286,7 +360,8 @@ __global__ __launch_bounds__(1024) void k_pcl_fps(const float* __restrict__ dept
   __shared__ float red_s[3][16];
   __shared__ float cen[3];
   const int inst = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int cnt = total[inst];
+  const int HW = H * W, frame = src.frame(inst);
+  const int cnt = pcl_count_ok(total[inst], frame, src.frames(), HW);
   long long* out = sample_out + (size_t)inst * N;
   unsigned L = cnt > 0 ? (unsigned)cnt : 0u;
   while (L && L < (unsigned)N) L <<= 1;
@@ -294,14 +369,17 @@ __global__ __launch_bounds__(1024) void k_pcl_fps(const float* __restrict__ dept
     for (int i = tid; i < N; i += 1024) out[i] = L ? (long long)((unsigned)i % L) : 0;
     return;
   }
+  const PclCam cam = src.cam(frame);
+  const float* depth_f = depth + (size_t)frame * HW;
   float* px = scratch + (size_t)inst * 4 * Lcap;
   float* py = px + Lcap;
   float* pz = py + Lcap;
   float* dist = pz + Lcap;
   float sx = 0.f, sy = 0.f, sz = 0.f;
   for (unsigned j = tid; j < L; j += 1024) {
-    float x, y, z;
-    pcl_point(depth, cand[(size_t)inst * H * W + (j % (unsigned)cnt)], W, cam, x, y, z);
+    float x = 0.f, y = 0.f, z = 0.f;
+    const int pix = cand[(size_t)inst * HW + (j % (unsigned)cnt)];
+    if ((unsigned)pix < (unsigned)HW) pcl_point(depth_f, pix, W, cam, x, y, z);
     px[j] = x;
     py[j] = y;
     pz[j] = z;
@@ -361,6 +439,9 @@ __global__ __launch_bounds__(1024) void k_pcl_fps(const float* __restrict__ dept
           v = red_v[w];
           i = red_i[w];
         }
+      // every distance NaN (non-finite depth): no maximum was found.  The reference's argmax of an all-NaN tensor is
+      // its first index.
+      if ((unsigned)i >= L) i = 0;
       out[it] = i;
       cen[0] = px[i];
       cen[1] = py[i];

@@ -1,5 +1,5 @@
-// C ABI of the frame-batched point-cloud preparation and the depth augmentation (kernels: catre_pclf.h, the
-// single-frame kernels and the workspace layout they share: catre_pcl.h and catre_pcl_api.inc;
+// C ABI of the frame-batched point-cloud preparation and the depth augmentation (kernels: catre_pcl.h on its
+// PclFrameTable source, catre_pclf.h for the augmentation; workspace layout and launch helpers: catre_pcl_api.inc;
 // declarations: include/catre_hip.h)
 namespace {
 // head of the workspace: the per-instance and per-frame tables the entry points stage, then the single-frame layout
@@ -58,6 +58,11 @@ int pclf_stage(const PclfWs& L, int* ws, const float* K, const int32_t* frame_of
     return CATRE_ERR_LAUNCH;
   return CATRE_OK;
 }
+// the staged head as the kernels' frame source
+inline PclFrameTable pclf_table(const PclfWs& L, const int* ws, int F) {
+  return PclFrameTable{ws + L.frame_of, ws + L.rank_of, (const PclCam*)(ws + L.cams),
+                       (const unsigned long long*)(ws + L.seeds), F};
+}
 }  // namespace
 
 size_t catre_pclf_workspace_bytes(int F, int I, int H, int W) {
@@ -77,33 +82,16 @@ int catre_pclf_candidates(const float* depth, const float* K, const int32_t* fra
   int* ws = (int*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (int e = pclf_stage(L, ws, K, frame_of, nullptr, labels ? label_of : nullptr, nullptr, F, I, st)) return e;
-  const int* fo = ws + L.frame_of;
+  const PclFrameTable src = pclf_table(L, ws, F);
   const int* lo = ws + L.label_of;
-  const PclCam* cams = (const PclCam*)(ws + L.cams);
   int* body = ws + L.head_ints;
-  const PclWs& B = L.body;
-  const dim3 grid(B.nchunks, I), block(256);
-#define PCLF_CAND(MODE, LT)                                                                                           \
-  do {                                                                                                                \
-    hipLaunchKernelGGL((k_pclf_count<MODE, LT>), grid, block, 0, st, depth, masks, (const LT*)labels, fo, lo, cams,   \
-                       poses, scales, ratio, use_ball, H, W, B.nchunks, body + B.bins);                               \
-    hipLaunchKernelGGL(k_pcl_pick, dim3(I), dim3(256), 0, st, body + B.bins, B.nchunks, 1, body + B.choose,           \
-                       body + B.offsets, body + B.total);                                                             \
-    hipLaunchKernelGGL((k_pclf_compact<MODE, LT>), grid, block, 0, st, depth, masks, (const LT*)labels, fo, lo, cams, \
-                       poses, scales, ratio, use_ball, H, W, B.nchunks, body + B.choose, body + B.offsets,            \
-                       body + B.cand);                                                                                \
-  } while (0)
-  if (!labels)
-    PCLF_CAND(0, unsigned char);
-  else if (label_bytes == 1)
-    PCLF_CAND(1, unsigned char);
-  else
-    PCLF_CAND(1, int);
+#define PCLF_CAND(MODE, LT)                                                                                          \
+  pcl_run_candidates<MODE, LT>(src, depth, masks, labels, lo, poses, scales, ratio, use_ball, I, H, W, L.body, body, \
+                               counts_out, st)
+  if (!labels) return PCLF_CAND(0, unsigned char);
+  if (label_bytes == 1) return PCLF_CAND(1, unsigned char);
+  return PCLF_CAND(1, int);
 #undef PCLF_CAND
-  if (counts_out &&
-      hipMemcpyAsync(counts_out, body + B.total, (size_t)I * sizeof(int), hipMemcpyDeviceToDevice, st) != hipSuccess)
-    return CATRE_ERR_LAUNCH;
-  return check_launch();
 }
 
 int catre_pclf_sample(const float* depth, const float* K, const int32_t* frame_of, const int32_t* rank_of,
@@ -117,12 +105,8 @@ int catre_pclf_sample(const float* depth, const float* K, const int32_t* frame_o
   int* ws = (int*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (int e = pclf_stage(L, ws, K, frame_of, rank_of, nullptr, seeds, F, I, st)) return e;
-  const int* body = ws + L.head_ints;
-  hipLaunchKernelGGL(k_pclf_gather, dim3((N + 255) / 256, I), dim3(256), 0, st, depth, (const int*)(ws + L.frame_of),
-                     (const int*)(ws + L.rank_of), (const PclCam*)(ws + L.cams),
-                     (const unsigned long long*)(ws + L.seeds), F, H, W, body + L.body.cand, body + L.body.total,
-                     sample_idx, N, pcl_out, pix_out);
-  return check_launch();
+  return pcl_run_gather(pclf_table(L, ws, F), depth, I, H, W, L.body, ws + L.head_ints, sample_idx, N, pcl_out, pix_out,
+                        st);
 }
 
 int catre_pclf_fps(const float* depth, const float* K, const int32_t* frame_of, void* workspace, size_t ws_bytes, int F,
@@ -135,11 +119,8 @@ int catre_pclf_fps(const float* depth, const float* K, const int32_t* frame_of, 
   int* ws = (int*)workspace;
   hipStream_t st = (hipStream_t)stream;
   if (int e = pclf_stage(L, ws, K, frame_of, nullptr, nullptr, nullptr, F, I, st)) return e;
-  const int* body = ws + L.head_ints;
-  hipLaunchKernelGGL(k_pclf_fps, dim3(I), dim3(1024), 0, st, depth, (const int*)(ws + L.frame_of),
-                     (const PclCam*)(ws + L.cams), F, H, W, body + L.body.cand, body + L.body.total, N, scratch, slot_cap,
-                     sample_idx_out);
-  return check_launch();
+  return pcl_run_fps(pclf_table(L, ws, F), depth, I, H, W, L.body, ws + L.head_ints, N, scratch, slot_cap,
+                     sample_idx_out, st);
 }
 
 int catre_depth_augment(const void* depth_in, int in_is_u16, float depth_div, const catre_depth_aug_frame* frames,

@@ -44,6 +44,34 @@ def _random_sample(n, npoint):
     return idx
 
 
+def _byte_masks(masks):
+    """bool / uint8 masks -> the contiguous uint8 the kernels read"""
+    return (masks.to(torch.uint8) if masks.dtype == torch.bool else masks).contiguous()
+
+
+def _tiled(c, num_points):
+    """``while len(idx) < num_points: idx = cat([idx, idx])``: the length of the tiled candidate list"""
+    while c < num_points:
+        c *= 2
+    return c
+
+
+def _require_candidates(counts, who=lambda j: "an instance"):
+    for j, c in enumerate(counts):
+        if c == 0:
+            # the reference recurses with a 1.2x larger ratio for ever here (cat_data_utils.py:390-393)
+            raise ValueError(f"{who(j)} has no masked pixel with depth > 0")
+
+
+def _host_draws(counts, num_points, use_ball):
+    """The reference's draws, instance by instance in the order given (= the data loader's loop order) -> [I,num_points].
+    Ball crop: the candidate list is tiled until it holds num_points entries, then one permutation
+    (cat_data_utils.py:301-309, 322-329); crop_mask_depth_image: random_sample tops a short list up with further
+    permutations."""
+    return torch.stack([torch.randperm(_tiled(c, num_points))[:num_points] if use_ball else _random_sample(c, num_points)
+                        for c in counts])
+
+
 def sample_instances(depth, K, masks, poses=None, scales=None, ratio=0.5, num_points=1024, use_ball=True, sample="host",
                      seed=0, fps_sample=False, return_pixels=False):
     """depth [H,W] (device fp32, metres), K 3x3, masks [I,H,W] bool/uint8 (or None: whole frame, I from poses),
@@ -57,11 +85,9 @@ def sample_instances(depth, K, masks, poses=None, scales=None, ratio=0.5, num_po
     H, W = depth.shape
     dev = depth.device
     if masks is not None:
-        if masks.dtype == torch.bool:
-            masks = masks.to(torch.uint8)
-        if masks.dtype != torch.uint8 or masks.device != dev or masks.shape[1:] != (H, W):
+        if masks.dtype not in (torch.bool, torch.uint8) or masks.device != dev or masks.shape[1:] != (H, W):
             raise ValueError("masks must be [I,H,W] bool / uint8 on the depth map's device")
-        masks = masks.contiguous()
+        masks = _byte_masks(masks)
         I = masks.shape[0]
     else:
         I = poses.shape[0]
@@ -81,36 +107,19 @@ def sample_instances(depth, K, masks, poses=None, scales=None, ratio=0.5, num_po
                                        int(bool(use_ball)), I, H, W, hip.ptr(ws), nbytes, hip.ptr(counts), st),
               "catre_pcl_candidates")
     sidx = None
+    if fps_sample or sample == "host":
+        cl = counts.cpu().tolist()
+        _require_candidates(cl)
     if fps_sample:
         # INPUT.FPS_SAMPLE: farthest point sampling of the tiled candidate list (cat_data_utils.py:305-306 with
         # device="cpu" as the data loader passes -> farthest_points_torch.py:6-62), one workgroup per instance
-        cl = counts.cpu().tolist()
-        if min(cl) == 0:
-            raise ValueError("an instance has no masked pixel with depth > 0")
-        cap = 0
-        for c in cl:
-            L = c
-            while L < num_points:
-                L *= 2
-            cap = max(cap, L)
+        cap = max(_tiled(c, num_points) for c in cl)
         scratch = torch.empty(I * 4 * cap, dtype=torch.float32, device=dev)
         sidx = torch.empty(I, num_points, dtype=torch.int64, device=dev)
         hip.check(lib.catre_pcl_fps(hip.ptr(depth), k9, hip.ptr(ws), nbytes, I, H, W, num_points, hip.ptr(scratch), cap,
                                     hip.ptr(sidx), st), "catre_pcl_fps")
     elif sample == "host":
-        rows = []
-        for c in counts.cpu().tolist():  # instance order = the data loader's loop order
-            if c == 0:
-                # the reference recurses with a 1.2x larger ratio for ever here (cat_data_utils.py:390-393)
-                raise ValueError("an instance has no masked pixel with depth > 0")
-            if use_ball:  # the candidate list is tiled until it holds num_points entries, then one permutation
-                L = c
-                while L < num_points:
-                    L *= 2
-                rows.append(torch.randperm(L)[:num_points])  # cat_data_utils.py:301-309, 322-329
-            else:        # crop_mask_depth_image: random_sample tops a short list up with further permutations
-                rows.append(_random_sample(c, num_points))
-        sidx = torch.stack(rows).to(dev)
+        sidx = _host_draws(cl, num_points, use_ball).to(dev)
     pcl = torch.empty(I, num_points, 3, dtype=torch.float32, device=dev)
     pix = torch.empty(I, num_points, dtype=torch.int32, device=dev) if return_pixels else None
     hip.check(lib.catre_pcl_sample(hip.ptr(depth), k9, hip.ptr(ws), nbytes, hip.ptr(sidx), int(seed) & (2**64 - 1), I, H, W,
@@ -164,12 +173,6 @@ def _per_frame(v, F, name, cast):
             raise ValueError(f"{name}: expected one value or {F} (one per frame), got {len(v)}")
         return [cast(x) for x in v]
     return [cast(v)] * F
-
-
-def _tiled(c, num_points):
-    while c < num_points:
-        c *= 2
-    return c
 
 
 def sample_frames(depth, K, frame_of, poses, scales, masks=None, labels=None, label_of=None, ratio=0.5, num_points=1024,
@@ -242,7 +245,7 @@ def sample_frames(depth, K, frame_of, poses, scales, masks=None, labels=None, la
     else:
         if masks.device != dev:
             raise ValueError("masks must be on the depth maps' device")
-        masks = (masks.to(torch.uint8) if masks.dtype == torch.bool else masks).contiguous()
+        masks = _byte_masks(masks)
         label_bytes = 0
     poses = hip.require_dev_f32(poses.contiguous(), "poses", (I, 3, 4))
     scales = hip.require_dev_f32(scales.contiguous(), "scales", (I, 3))
@@ -283,10 +286,7 @@ def sample_frames(depth, K, frame_of, poses, scales, masks=None, labels=None, la
         sidx = None
         if fps_sample or sample == "host":
             cl = counts[s:e].cpu().tolist()   # the one device->host copy of the batch (of the group)
-            for j, c in enumerate(cl):
-                if c == 0:
-                    # the reference recurses with a 1.2x larger ratio for ever here (cat_data_utils.py:390-393)
-                    raise ValueError(f"instance {s + j} (frame {fo[s + j]}) has no masked pixel with depth > 0")
+            _require_candidates(cl, lambda j: f"instance {s + j} (frame {fo[s + j]})")
         if fps_sample:
             cap = max(_tiled(c, num_points) for c in cl)
             scratch = torch.empty(n * 4 * cap, dtype=torch.float32, device=dev)
@@ -294,9 +294,7 @@ def sample_frames(depth, K, frame_of, poses, scales, masks=None, labels=None, la
             _call("catre_pclf_fps", hip.ptr(depth), k9, fo_c, hip.ptr(ws), nb, F, n, H, W, num_points, hip.ptr(scratch), cap,
                   hip.ptr(sidx), st)
         elif sample == "host":   # the draws of sample_instances, instance by instance in the order given
-            rows = [torch.randperm(_tiled(c, num_points))[:num_points] if use_ball else _random_sample(c, num_points)
-                    for c in cl]
-            sidx = torch.stack(rows).to(dev)
+            sidx = _host_draws(cl, num_points, use_ball).to(dev)
         _call("catre_pclf_sample", hip.ptr(depth), k9, fo_c, i32(ranks[s:e]), hip.ptr(ws), nb, hip.ptr(sidx), seeds_c, F, n,
               H, W, num_points, hip.ptr(pcl[s:e]), hip.ptr(pix[s:e]) if return_pixels else None, st)
     if return_pixels:

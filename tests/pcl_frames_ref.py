@@ -57,6 +57,60 @@ def augment(raw_or_metres, fill=None, keep=None, ratio=None, level=None, gauss=N
     return out
 
 
+PERM_SHAPES = ((48, 40), (72, 64))             # one ragged 4096-pixel chunk / one full chunk and a ragged one
+PERM_POINTS = 64
+PERM_SEEDS = (0, 2 ** 63 + 5)                  # the seed of frame 0 / of frame 1
+
+
+def perm_scene(H, W, seed):
+    """One small frame for the device-permutation pin (``tests/golden/pcl_device_perm.npz``) -> dict of CPU tensors: a wall
+    at about 1 m with a few holes, three half-full random masks, and balls of three sizes - the first holds between 10
+    and ``PERM_POINTS`` candidates (the list is tiled), the other two hold more."""
+    g = torch.Generator().manual_seed(1000 * H + seed)
+    depth = 1.0 + 0.05 * torch.rand(H, W, generator=g)
+    depth[torch.rand(H, W, generator=g) < 0.03] = 0.0
+    K = torch.tensor([[60.0, 0.0, W / 2 - 0.5], [0.0, 62.0, H / 2 - 0.5], [0.0, 0.0, 1.0]])
+    masks = torch.rand(3, H, W, generator=g) < 0.5
+    poses = torch.zeros(3, 3, 4)
+    for i, (u, v) in enumerate(((W / 4, H / 2), (W / 2, H / 2), (3 * W / 4, H / 3))):
+        poses[i, :, :3] = torch.eye(3)
+        poses[i, :, 3] = torch.tensor([(u - K[0, 2]) / K[0, 0] * 1.02, (v - K[1, 2]) / K[1, 1] * 1.02, 1.02])
+    scales = torch.tensor([[0.1] * 3, [0.5] * 3, [0.3] * 3])
+    return dict(depth=depth, K=K, masks=masks, poses=poses, scales=scales)
+
+
+def perm_batch(H, W):
+    """the two frames of a shape as ``sample_frames`` takes them, instances frame by frame"""
+    sc = [perm_scene(H, W, f) for f in range(2)]
+    cat = lambda k: torch.cat([s[k] for s in sc])
+    return dict(depth=torch.stack([s["depth"] for s in sc]), K=torch.stack([s["K"] for s in sc]), frame_of=[0] * 3 + [1] * 3,
+                masks=cat("masks"), poses=cat("poses"), scales=cat("scales"))
+
+
+def device_perm_outputs(dev="cuda:0"):
+    """``sample="device"`` of the build that is loaded, on both shapes and both crops -> {name: array}: per shape
+    ``frames_*`` from one ``sample_frames`` call on the two frames and ``inst_*`` from ``sample_instances`` frame by frame
+    (rows in the same order), each as counts, pixel indices and the points' bit patterns."""
+    from catre_amd import pcl_prep
+
+    bits = lambda t: t.cpu().contiguous().view(torch.int32).numpy().copy()
+    out = {}
+    for H, W in PERM_SHAPES:
+        b = perm_batch(H, W)
+        d = {k: v.to(dev) for k, v in b.items() if k not in ("K", "frame_of")}
+        for ball in (True, False):
+            kw = dict(num_points=PERM_POINTS, use_ball=ball, sample="device", return_pixels=True)
+            got = {"frames": pcl_prep.sample_frames(d["depth"], b["K"], b["frame_of"], d["poses"], d["scales"], masks=d["masks"],
+                                                    seed=list(PERM_SEEDS), **kw)}
+            per = [pcl_prep.sample_instances(d["depth"][f], b["K"][f], d["masks"][3 * f:3 * f + 3], d["poses"][3 * f:3 * f + 3],
+                                             d["scales"][3 * f:3 * f + 3], seed=PERM_SEEDS[f], **kw) for f in range(2)]
+            got["inst"] = tuple(torch.cat([p[k] for p in per]) for k in range(3))
+            for who, (pcl, pix, counts) in got.items():
+                tag = f"{who}_{H}x{W}_{'ball' if ball else 'mask'}"
+                out[tag + "_pcl_bits"], out[tag + "_pix"], out[tag + "_counts"] = bits(pcl), pix.cpu().numpy(), counts.cpu().numpy()
+    return out
+
+
 def frames_loop(depth, K, frame_of, masks, poses, scales, ratio=0.5, num_points=1024, use_ball=True, sample_idx=None,
                 fps=False):
     """depth [F,H,W], K [3,3] / [F,3,3], masks [I,H,W] bool (CPU tensors) -> dict(counts [I], pcl [I,N,3], pix [I,N]):
