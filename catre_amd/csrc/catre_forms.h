@@ -91,6 +91,32 @@ inline bool screen_epi() {
   return v != 0;
 }
 
+// `screen_da` (SW_DA, CATRE_SCREEN_DA) and its STN arm (SW_DA_STN, CATRE_SCREEN_DA_STN; counts while `screen_da` is on):
+// the fp16 screen's eps with the activations' rounding MEASURED per tile and the weights' error sign-split
+// (catre_screen.h) - a runtime flag of the same fp16-screen kernels, no form and no kernel of its own; off is the
+// shipped eps bit for bit.  Fewer candidates reach the replay; the outputs keep their bits either way.
+#ifndef CATRE_SCREEN_DA_DEFAULT
+#define CATRE_SCREEN_DA_DEFAULT true
+#endif
+#ifndef CATRE_SCREEN_DA_STN_DEFAULT
+#define CATRE_SCREEN_DA_STN_DEFAULT false
+#endif
+constexpr int SW_DA = SW_COUNT + 1, SW_DA_STN = SW_COUNT + 2;
+inline std::atomic<int> g_screen_da{-1}, g_screen_da_stn{-1};
+inline int env_switch(std::atomic<int>& g, const char* env, bool dflt) {
+  int v = g.load(std::memory_order_relaxed);
+  if (v < 0) {
+    const char* e = getenv(env);
+    v = e ? atoi(e) != 0 : dflt;
+    g.store(v, std::memory_order_relaxed);
+  }
+  return v;
+}
+inline int screen_da() { return env_switch(g_screen_da, "CATRE_SCREEN_DA", CATRE_SCREEN_DA_DEFAULT); }
+inline int screen_da_stn() {
+  return screen_da() && env_switch(g_screen_da_stn, "CATRE_SCREEN_DA_STN", CATRE_SCREEN_DA_STN_DEFAULT);
+}
+
 // the raw switch word: read from the environment once, ids 0 - 9 then follow catre_form_switch
 inline std::atomic<int> g_forms{-1};
 inline int forms() {
@@ -299,9 +325,9 @@ inline PackLayout pack_layout(int ts_in) {
   L.s16_c4 = take(1024 * 512 / 2);
   L.s16_stn_c3 = take(1024 * 128 / 2);
   L.s16_fstn_c3 = take(1024 * 128 / 2);
-  L.s16_uw4 = take(2 * 1024);  // 2^-scale, then the rows' rounding errors (k_screen_f16_dw)
-  L.s16_uw_stn = take(2 * 1024);
-  L.s16_uw_fstn = take(2 * 1024);
+  L.s16_uw4 = take(3 * 1024);  // 2^-scale, then the rows' rounding errors and their sign-split form (k_screen_f16_dw)
+  L.s16_uw_stn = take(3 * 1024);
+  L.s16_uw_fstn = take(3 * 1024);
   // everything above is independent of ts_in (the stage entry points rely on that)
   L.ts_w0t = take((size_t)ts_in * 256);
   L.ts_w1t = take(256 * 256);

@@ -218,8 +218,8 @@ int launch_stn3d(const EncCall& c, const float* const* prm, const float* packed,
   FormDecision d;
   if (const int rc = decide(STAGE_STN3D, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
   const Stn3dW w = stn3d_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));  // conv offsets do not depend on ts_in
-  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
-  const Stn3dRunArgs run{*c.pts, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, c.pm, w.sc.wps, w.sc.nw, c.B, c.N, c.M, d.S, w.sc.uw};
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw, screen_da_stn()};
+  const Stn3dRunArgs run{*c.pts, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, c.pm, w.sc.wps, w.sc.nw, c.B, c.N, c.M, d.S, w.sc.uw, sc.da};
   const dim3 grid(d.grid), block(256);
   ProfScope ps(CATRE_K_STN3D, c.st);
   switch (d.form) {
@@ -260,9 +260,9 @@ int launch_stnkd(const EncCall& c, const float* const* prm, const float* packed,
   FormDecision d;
   if (const int rc = decide(STAGE_STNKD, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
   const StnkdW w = stnkd_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));
-  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw, screen_da_stn()};
   const StnkdRunArgs run{*c.pts, c.trans3, w.wc1, w.bc1, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, c.pm, w.sc.wps, w.sc.nw,
-                         c.B, c.N, c.M, d.S, w.sc.uw};
+                         c.B, c.N, c.M, d.S, w.sc.uw, sc.da};
   const dim3 grid(d.grid), block(256);
   ProfScope ps(CATRE_K_STNKD, c.st);
   switch (d.form) {
@@ -303,7 +303,7 @@ int launch_trunk(const EncCall& c, const float* const* prm, const float* packed,
   FormDecision d;
   if (const int rc = decide(STAGE_TRUNK, split ? MODE_SPLIT : MODE_F32, false, false, probe_s != nullptr, c.B, c.N, c.M, &d)) return rc;
   const TrunkW w = trunk_weights(prm, packed, pack_layout(1), split ? PK_SPLIT : PK_F32, f16_screen(d));
-  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw};
+  const ScreenArgs sc{w.sc.wps, w.sc.nw, probe_s, probe_eps, w.sc.uw, screen_da()};
   const TrunkRunArgs run{*c.pts, c.trans3, c.trans64, w.w1, w.b1, w.w2, w.b2, w.w3, w.b3, w.w4, w.b4, c.pm, pointfeat,
                          g_trunk_trace, sc, frun, c.B, c.N, c.M, d.S};
   const dim3 grid(d.grid);
@@ -501,7 +501,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     hipLaunchKernelGGL(k_pack_screen_f16, dim3(1024 * 512 / 256), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
                        packed + L.scr_nw4, reinterpret_cast<unsigned short*>(packed + L.s16_c4), packed + L.s16_uw4);
     hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_CONV4_W], 512, 1024, 512,
-                       packed + L.scr_nw4, packed + L.s16_uw4 + 1024);
+                       packed + L.scr_nw4, packed + L.s16_uw4 + 1024, packed + L.s16_uw4 + 2048);
   }
   // the same of the two STNs' conv3 (k_stn3d_pair_s / k_stnkd_pair_s)
   frag_sp(prm[CATRE_P_STN_CONV3_W], 128, 1024, 128, L.scr_stn_c3);
@@ -513,7 +513,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
     hipLaunchKernelGGL(k_pack_screen_f16, dim3(1024 * 128 / 256), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
                        packed + L.scr_nw_stn, reinterpret_cast<unsigned short*>(packed + L.s16_stn_c3), packed + L.s16_uw_stn);
     hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_STN_CONV3_W], 128, 1024, 128,
-                       packed + L.scr_nw_stn, packed + L.s16_uw_stn + 1024);
+                       packed + L.scr_nw_stn, packed + L.s16_uw_stn + 1024, packed + L.s16_uw_stn + 2048);
   }
   if (prm[CATRE_P_FSTN_CONV3_W]) {
     hipLaunchKernelGGL(k_screen_wnorm, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
@@ -522,7 +522,7 @@ int catre_pack_weights_sel(const float* const* prm, int N, int M, int ts_in, flo
                        packed + L.scr_nw_fstn, reinterpret_cast<unsigned short*>(packed + L.s16_fstn_c3),
                        packed + L.s16_uw_fstn);
     hipLaunchKernelGGL(k_screen_f16_dw, dim3(1024 / 4), dim3(256), 0, st, prm[CATRE_P_FSTN_CONV3_W], 128, 1024, 128,
-                       packed + L.scr_nw_fstn, packed + L.s16_uw_fstn + 1024);
+                       packed + L.scr_nw_fstn, packed + L.s16_uw_fstn + 1024, packed + L.s16_uw_fstn + 2048);
   }
   }
   for (int h = 0; h < 2 && head32; ++h) {
@@ -1206,6 +1206,13 @@ int catre_form_switch(int id, int value) {
   if (id == SW_EPI) {  // not a bit of the form word: it picks the epilogue of the fp16-screen forms, not a form
     const int cur = screen_epi();
     if (value >= 0) g_screen_epi.store(value != 0, std::memory_order_relaxed);
+    return cur;
+  }
+  if (id == SW_DA || id == SW_DA_STN) {  // likewise: they pick the bound the same kernels select with
+    std::atomic<int>& g = id == SW_DA ? g_screen_da : g_screen_da_stn;
+    const int cur = env_switch(g, id == SW_DA ? "CATRE_SCREEN_DA" : "CATRE_SCREEN_DA_STN",
+                               id == SW_DA ? CATRE_SCREEN_DA_DEFAULT : CATRE_SCREEN_DA_STN_DEFAULT);
+    if (value >= 0) g.store(value != 0, std::memory_order_relaxed);
     return cur;
   }
   if (id < 0 || id >= SW_PUBLIC) return -1;

@@ -70,8 +70,8 @@
 //   conversion or flushed by the matrix pipe; the fp32 multiply by the scale may lose a denormal (2^-126): at most
 //   eta = 2^-13 per element on top of the rounding.
 //   The weights' rounding is KNOWN at pack time: dw_c = ||fp16(w'_c) - w'_c||_2 2^-sw_c (k_screen_f16_dw, summed in double,
-//   rounded up) replaces the worst case 2^-11 nw_c - it measures 0.42 of it on the recipe weights.  The activations' is not (a second
-//   pass over the image per tile would be needed).  With w~ = w' + dw + zeta_w, a~ = a' (1 + theta) + zeta_a, |theta| <=
+//   rounded up) replaces the worst case 2^-11 nw_c - it measures 0.42 of it on the recipe weights.  The activations' is taken at its
+//   worst case here and measured per tile under `screen_da` (next section).  With w~ = w' + dw + zeta_w, a~ = a' (1 + theta) + zeta_a, |theta| <=
 //   2^-11, |zeta| <= eta, A' = sum_k |w'| |a'| <= nw' na':
 //     * products:  sum_k |w~ a~ - w' a'| <= (1 + 2^-11) dw' na' + 2^-11 nw' na' + eta (1 + 2^-10) sqrt(K) (nw' + na'(p)) + K eta^2
 //     * w~ a~ is exact in fp32 (22 significant bits) and, where not zero, >= 2^-48: no fp32 underflow in the screen's sums
@@ -83,6 +83,40 @@
 //   with rk >= 2^-12 sqrt(K)  (2^-sa <= 2^-14 max_p na_p and uw_c <= 2^-14 nw_c unless clamped: delta is ~ 3e-4 of the gamma
 //   term for the tile's largest point).  infl as above with 2^-19 for the roundings of eps's own operations.
 //   An eps that overflows to +inf makes every point a candidate, as it must.
+//
+// The measured bound (switch `screen_da`, its STN arm `screen_da_stn`: a runtime flag of the same fp16-screen kernels)
+// --------------------------------------------------------------------------------------------------------------------
+// Two terms of the product error above are replaced by what the operands actually are; accumulation, the chain's own K u,
+// eta, delta and the unscalable regime keep their constants.
+//   Activations.  screen_row_norms already reads every element of the fp32 image once per tile; in the same pass it forms
+//     r_k = a_k - rne11(a_k)      (screen_rne11_err: a_k rounded to 11 significant bits, unbounded exponent)
+//   in integer arithmetic - add half an 11-bit ulp to the magnitude, drop 13 bits - and one exact fp32 subtraction: a_k - hi
+//   is a multiple of ulp(a_k) of at most 2^12 ulps, so it is representable; nothing can overflow while the row norms are
+//   below 2^64, which the scalable regime implies (a carry out of the largest exponent needs |a_k| >= 2^127).  A tie goes
+//   away from zero where v_cvt goes to even: the same |r_k|.  The tile scale 2^sa is a power of two and commutes with the
+//   rounding unless the scaled element falls below 2^-14 (fp16-subnormal, flushed, or an fp32 denormal): for such an
+//   element |a~_k - a'_k| <= eta whatever r_k measured, and eta sqrt(K) is in delta already.  So with
+//     da_p = sqrt(fl sum_k r_k^2) (1 + 2^-12)      (the fp32 sum: K u relative; a square below 2^-126 may be lost:
+//                                                   <= sqrt(K) 2^-63 <= 2^-58 absolute on da_p, carried as 2^-58 nw_c in e0)
+//     ||a~ - a'||_2 <= 2^sa (da_p + 2^-58) + eta sqrt(K),  and always ||rne11(a') - a'||_2 <= 2^-11 na'
+//   the term 2^-11 nw' na' becomes nw' da'.  Per tile rho_t = min(2^-11, max_p da_p / na_p) rounded up (screen_tile_rho; the
+//   division and the product: 1 + 2^-20), one scalar register across the sweep like sa, and
+//     gamma = rho_t + 2^-21 + 2 K 2^-23       (rho_t = 2^-11: the shipped gamma bit for bit)
+//   A per-point da_p in eps would cost a seventh instruction on each of the 256 accumulators; how far a point's own
+//   da_p / na_p sits below its tile's maximum on the recipe inputs is printed by tests/test_screen_da_host.py.
+//   Weights.  The three pooled layers read images written behind ReLU (a3 of the trunk, the conv2 images of both STNs:
+//   store_tile_lds_pre<.., RELU = true>), and fp16 rounding keeps the sign: a~_k >= 0.  With dW = fp16(w') - w' split into
+//   its positive and negative parts,
+//     |sum_k dW_k a~_k| = |sum_k dW^+_k a~_k - sum_k dW^-_k a~_k| <= max(||dW^+||, ||dW^-||) ||a~||  =: dws' ||a~||
+//   (both sums are >= 0, each <= its norm times ||a~||).  dws_c is known at pack time (k_screen_f16_dw, behind dw in the
+//   uw table) and measures 0.74 - 0.77 of dw_c on the recipe weights.  A layer whose image may hold negative elements must
+//   keep dw (tests/test_screen_da_host.py shows the violation); there is none among the screened layers.
+//   Together, for the scaled operands:
+//     sum_k |w~ a~ - w' a'| <= nw' da' + (1 + 2^-11) dws' na' + eta (1 + 2^-10) sqrt(K) (nw' + na') + K eta^2
+//     e1 = ((rho_t + 2^-21 + 2 K 2^-23) nw_c + (1 + 2^-10) dws_c + rk uw_c) infl,   eps = fmaf(e1, na_p, e0)
+//   infl divides by gamma: eps >= gamma |y| must hold for the smallest gamma that can occur, rho_t = 0, so
+//   infl = 1 + 2^-22 / (2^-21 + 2 K 2^-23) + 2^-18  (the rounding of rho_t + gamma0 is the extra 2^-19).
+//   Off: rho_t = 2^-11, dw for dws, the shipped infl and no measuring - the candidate sets of the parent, bit for bit.
 #pragma once
 #include "catre_split.h"
 
@@ -106,14 +140,24 @@ struct ScreenBoundF16 {
   static constexpr float gamma = 0x1p-11f + 0x1p-21f + 2.f * K * 0x1p-23f;
   static constexpr float rk = (K == 128 ? 11.32f : 22.63f) * 0x1p-12f;  // >= 2^-12 sqrt(K)
   static constexpr float infl = 1.f + 0x1p-22f / gamma + 0x1p-19f;
+  // `screen_da`: gamma = rho_t + gamma0 with the tile's measured rho_t in [0, 2^-11] (rho_t = 2^-11 gives `gamma` bit for
+  // bit); the inflation for the smallest gamma that can occur, rho_t = 0, and one rounding more (the sum rho_t + gamma0)
+  static constexpr float gamma0 = 0x1p-21f + 2.f * K * 0x1p-23f;
+  static constexpr float infl_da = 1.f + 0x1p-22f / gamma0 + 0x1p-18f;
+  static_assert(0x1p-11f + gamma0 == gamma, "switch off: the shipped gamma");
 };
 // eps = fmaf(e1, na, e0); uw = 2^-sw_c (k_pack_screen_f16), dw = the row's rounding error (k_screen_f16_dw), ua = 2^-sa
-// (screen_tile_scale)
+// (screen_tile_scale).  `screen_da` (da, wave-uniform): rho = the tile's measured rho_t (screen_tile_rho) and dw = the row's
+// sign-split error dws_c; off: rho = 2^-11 and dw = dw_c, the shipped eps bit for bit.
 template <int K>
-__device__ __forceinline__ void screen_eps_coef_f16(float nw, float uw, float dw, float ua, float& e1, float& e0) {
+__device__ __forceinline__ void screen_eps_coef_f16(float nw, float uw, float dw, float ua, float rho, bool da, float& e1,
+                                                    float& e0) {
   typedef ScreenBoundF16<K> SB;
-  e1 = fmaf(SB::gamma, nw, fmaf(1.f + 0x1p-10f, dw, SB::rk * uw)) * SB::infl;
-  e0 = fmaf(SB::rk * nw, ua, fmaf(K * 0x1p-24f * uw, ua, K * 0x1p-122f)) * SB::infl;
+  const float infl = da ? SB::infl_da : SB::infl;
+  e1 = fmaf(rho + SB::gamma0, nw, fmaf(1.f + 0x1p-10f, dw, SB::rk * uw)) * infl;
+  float t = fmaf(K * 0x1p-24f * uw, ua, K * 0x1p-122f);
+  if (da) t = fmaf(0x1p-58f, nw, t);  // squares below 2^-126 the measuring sum lost: <= sqrt(K) 2^-63 on da_p
+  e0 = fmaf(SB::rk * nw, ua, t) * infl;
 }
 // scale exponent of an operand whose norm bound is n: n 2^s in [2^14, 2^15), at most 60; below -60 the operand cannot be
 // kept inside fp16 (also n = inf / NaN)
@@ -159,24 +203,38 @@ __global__ __launch_bounds__(256) void k_pack_screen_f16(const float* __restrict
 }
 
 // dw[row] >= ||fp16(w') - w'||_2 2^-sw of the row as k_pack_screen_f16 rounds it: one wave per row, double accumulation,
-// rounded up (0 for a row that cannot be scaled: its channel takes every point)
+// rounded up (0 for a row that cannot be scaled: its channel takes every point).
+// dws[row] >= max(||dW^+||_2, ||dW^-||_2) 2^-sw, dW^+ / dW^- the positive / negative parts of the same rounding errors
+// (`screen_da`): against an image with no negative element, |sum_k dW_k a_k| <= max(sum_k dW^+_k a_k, sum_k dW^-_k a_k).
 __global__ __launch_bounds__(256) void k_screen_f16_dw(const float* __restrict__ W, int ld, int rows, int K,
-                                                       const float* __restrict__ nw, float* __restrict__ dw) {
+                                                       const float* __restrict__ nw, float* __restrict__ dw,
+                                                       float* __restrict__ dws) {
   const int row = blockIdx.x * 4 + (threadIdx.x >> 6), lane = threadIdx.x & 63;
   if (row >= rows) return;
   const int sw = screen_f16_exp(nw[row]);
-  double s = 0.0;
+  double s = 0.0, sp = 0.0, sn = 0.0;
   if (sw >= -60) {
     const float f = screen_pow2(sw);
     for (int k = lane; k < K; k += 64) {
       const float w = W[(size_t)row * ld + k] * f;
       const double r = (double)w - (double)(float)(_Float16)w;
       s += r * r;
+      if (r > 0.0)
+        sp += r * r;
+      else
+        sn += r * r;
     }
   }
 #pragma unroll
-  for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-  if (lane == 0) dw[row] = sw >= -60 ? (float)(sqrt(s) * (double)screen_pow2(-sw)) * (1.f + 0x1p-21f) : 0.f;
+  for (int o = 32; o > 0; o >>= 1) {
+    s += __shfl_xor(s, o);
+    sp += __shfl_xor(sp, o);
+    sn += __shfl_xor(sn, o);
+  }
+  if (lane == 0) {
+    dw[row] = sw >= -60 ? (float)(sqrt(s) * (double)screen_pow2(-sw)) * (1.f + 0x1p-21f) : 0.f;
+    dws[row] = sw >= -60 ? (float)(sqrt(sp > sn ? sp : sn) * (double)screen_pow2(-sw)) * (1.f + 0x1p-21f) : 0.f;
+  }
 }
 
 struct ScreenArgs {
@@ -185,7 +243,8 @@ struct ScreenArgs {
   const float* nw;    // [rows] weight-row norms (k_screen_wnorm)
   float* probe_s;     // tests only (catre_trunk_screen_probe): [tile][channel][point] screen value and bound, or NULL
   float* probe_eps;
-  const float* uw;    // fp16 screen: [rows] 2^-sw (k_pack_screen_f16), then [rows] dw (k_screen_f16_dw)
+  const float* uw;    // fp16 screen: [rows] 2^-sw (k_pack_screen_f16), then [rows] dw and [rows] dws (k_screen_f16_dw)
+  int da;             // fp16 screen: `screen_da` - the activations' rounding measured per tile, the sign-split dws for dw
 };
 
 #ifdef CATRE_DEBUG_TRACE
@@ -246,14 +305,48 @@ __device__ unsigned long long* g_screen_trace = nullptr;
 // Row addressing of the fp32 LDS image a screened layer reads: SWZ = the XOR-swizzled [rows][C] image of the trunk (pitch
 // C, chunk c of row r at c ^ (r & 15)), otherwise a padded image of pitch `ld` (the STN kernels' [128][LD128]).
 // ||a(p)||_2 (rounded up) of the ROWS rows of the image -> na[ROWS]; NT threads, NT/ROWS per row
+// `screen_da` (da, workgroup-uniform; rho = LDS [ROWS]): the same pass also measures the fp16 rounding of every element,
+// r = x - rne11(x) (screen_rne11_err), and leaves rho[row] >= ||r||_2 / na[row] (see the header; screen_tile_rho reduces it)
+__device__ __forceinline__ float screen_rne11_err(float x) {
+  // x rounded to 11 significant bits by dropping 13 of the 24 (half an 11-bit ulp added to the magnitude first: a tie
+  // goes away from zero where v_cvt_pk_f16_f32 goes to even - the same distance); a carry moves into the exponent
+  // field as it should.  x - hi is a multiple of ulp(x) of at most 2^12 ulps: the subtraction is exact.
+  return x - __uint_as_float((__float_as_uint(x) + 0x1000u) & 0xffffe000u);
+}
 template <int C, int NT, int ROWS = 64, bool SWZ = true>
-__device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, float* __restrict__ na, int tid, int ld = C) {
+__device__ __forceinline__ void screen_row_norms(const float* __restrict__ img, float* __restrict__ na, int tid, int ld = C,
+                                                 bool da = false, float* __restrict__ rho = nullptr) {
   constexpr int PER = NT / ROWS, CH = C / 4 / PER;  // chunks of 4 floats per thread
   static_assert(CH % 16 == 0, "a thread's chunks are whole swizzle groups");
   const int row = tid / PER, part = tid % PER;
   const float* r = img + row * ld + part * CH * 4;
   const int key = SWZ ? row & 15 : 0;
   float s = 0.f;
+  if (da) {
+    float d = 0.f;
+#pragma unroll 8
+    for (int j = 0; j < CH; ++j) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(r + ((j ^ key) << 2));
+#pragma unroll
+      for (int q = 0; q < 4; ++q) {
+        const float e = screen_rne11_err(v[q]);
+        s = fmaf(v[q], v[q], s);
+        d = fmaf(e, e, d);
+      }
+    }
+#pragma unroll
+    for (int o = 1; o < PER; o <<= 1) {
+      s += lane_get(s, tid ^ o);
+      d += lane_get(d, tid ^ o);
+    }
+    if (part == 0) {
+      const float n = fmaf(sqrtf(s), 1.f + 0x1p-12f, 0x1p-58f);
+      na[row] = n;
+      // (1 + 2^-12) as for na: the fp32 sum's K u and the square root; 2^-20: the division and the product
+      rho[row] = sqrtf(d) * (1.f + 0x1p-12f) / n * (1.f + 0x1p-20f);
+    }
+    return;
+  }
 #pragma unroll 8
   for (int j = 0; j < CH; ++j) {  // physical chunk j ^ (row & 15): the 16 rows of a lane group hit 16 distinct bank slots
     const f32x4 v = *reinterpret_cast<const f32x4*>(r + ((j ^ key) << 2));
@@ -367,6 +460,20 @@ __device__ __forceinline__ int screen_tile_scale(const float* na, int lane) {
   for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, lane_get(m, lane ^ o));
   const int s = screen_f16_exp(m);
   return __builtin_amdgcn_readfirstlane(s < -61 ? -61 : s);
+}
+
+// `screen_da`: rho_t = min(2^-11, max_p rho[p]) of the tile's 64 rows (screen_row_norms), wave-uniform in a scalar register
+// across the sweep like sa; off: 2^-11, the worst case, and rho is not read.  (A NaN row - inputs outside the contract - is
+// skipped by fmaxf, all NaN gives 2^-11.)
+__device__ __forceinline__ float screen_tile_rho(const float* rho, int lane, bool da) {
+  float m = 0x1p-11f;
+  if (da) {
+    m = rho[lane & 63];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) m = fmaxf(m, lane_get(m, lane ^ o));
+    m = fminf(m, 0x1p-11f);
+  }
+  return __builtin_bit_cast(float, __builtin_amdgcn_readfirstlane(__builtin_bit_cast(int, m)));
 }
 
 // The fp16 sweep of the same MB8 x NB2 wave tile: ONE product per (m-block, n-block, K = 16 chunk), one weight stream
@@ -807,7 +914,7 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
                                                     unsigned long long* sets, float* __restrict__ out,
                                                     const float* __restrict__ bias, int ch0, bool relu, int valid, int tile,
                                                     const ScreenArgs& sc, int lane, int ld = K, float* frun = nullptr,
-                                                    bool first = true, int sa = 0) {
+                                                    bool first = true, int sa = 0, float rho = 0x1p-11f) {
   static_assert(POOL || !RUN, "the run form refines the pooled replay");
   static_assert(POOL || !F16, "the fp16 screen exists for the pooled forms");
   static_assert(!EPI || (POOL && F16), "the lean epilogue exists for the pooled fp16-screen forms");
@@ -853,14 +960,14 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) {
         uwv[mb] = sc.uw[ch0 + mb * 32 + n];
-        dwv[mb] = sc.uw[1024 + ch0 + mb * 32 + n];
+        dwv[mb] = sc.uw[(sc.da ? 2048 : 1024) + ch0 + mb * 32 + n];
         nwv[mb] = nw[ch0 + mb * 32 + n];
       }
       const float ua = screen_pow2(sa < -60 ? 60 : -sa);
       float hv[2][32], Lown[2], Loth[2];
       auto pass1 = [&](int mb, float(&hi)[32]) {
         float e1, e0;
-        screen_eps_coef_f16<K>(nwv[mb], uwv[mb], dwv[mb], ua, e1, e0);
+        screen_eps_coef_f16<K>(nwv[mb], uwv[mb], dwv[mb], ua, rho, sc.da != 0, e1, e0);
         const float u = uwv[mb] * ua;
         float L = -INFINITY;
         if constexpr (RUN) L = fc[mb];
@@ -910,7 +1017,7 @@ __device__ __forceinline__ void screen_select_store(const f32x16 (&acc)[MB][2], 
       if constexpr (F16) {
         const float uw = sc.uw[ch0 + mb * 32 + n], ua = screen_pow2(sa < -60 ? 60 : -sa);
         all = sa < -60 || !(uw <= 0x1p60f);
-        screen_eps_coef_f16<K>(nw[ch0 + mb * 32 + n], uw, sc.uw[1024 + ch0 + mb * 32 + n], ua, e1, e0);
+        screen_eps_coef_f16<K>(nw[ch0 + mb * 32 + n], uw, sc.uw[(sc.da ? 2048 : 1024) + ch0 + mb * 32 + n], ua, rho, sc.da != 0, e1, e0);
         u = uw * ua;
       } else {
         screen_eps_coef<K>(nw[ch0 + mb * 32 + n], e1, e0);
@@ -1048,20 +1155,25 @@ struct Trunk4ScreenT {
   const float* b4;
   typename ScreenPipeSel<F16, ScreenPipeF16<5, 2>, ScreenPipe8<2>>::type g4;
   int sa;  // fp16 screen: the tile's scale exponent (screen_tile_scale), a scalar register across the sweep
+  float rho;  // ... and the tile's measured rounding rho_t (screen_tile_rho; 2^-11 with `screen_da` off)
   f32x16 acc4[8][2];
   __device__ __forceinline__ void prefetch(const f32x4* __restrict__ wp4, const float* __restrict__ b4_, int mb0, int lane) {
     wf = wp4 + ((size_t)mb0 * 64) * 64 + (lane & 31);
     b4 = b4_;
     g4.prefetch(sc.wps + ((size_t)mb0 * 32) * 64 + lane);
   }
-  // a2 (32 KiB, dead): [0, 64) the row norms, from float 64 on the waves' candidate sets (4 x 4 KiB)
+  // a2 (32 KiB, dead): [0, 64) the row norms, from float 64 on the waves' candidate sets (4 x 4 KiB), behind them
+  // [4160, 4224) the rows' rho (`screen_da`).  a3 is written behind ReLU (trunk4_body: store_tile_lds_pre<.., RELU = true>):
+  // no negative element, which the sign-split dws needs.
   __device__ __forceinline__ void sweep(const float* a3, float* a2, int tid, int lane) {
-    screen_row_norms<512, 256>(a3, a2, tid);
+    const bool da = F16 && sc.da != 0;
+    screen_row_norms<512, 256>(a3, a2, tid, 512, da, a2 + 64 + 4 * 1024);
     __syncthreads();
 #pragma unroll
     for (int mb = 0; mb < 8; ++mb) acc4[mb][0] = acc4[mb][1] = zero16();
     if constexpr (F16) {
       sa = screen_tile_scale(a2, lane);
+      rho = screen_tile_rho(a2 + 64 + 4 * 1024, lane, da);
       g4.run(acc4, a3, lane, sa);
     } else {
       g4.run(acc4, a3, lane);
@@ -1075,7 +1187,8 @@ struct Trunk4ScreenT {
     // value too many: without this line the kernel spills to scratch, which tests/test_resources.py reports.
     asm volatile("v_mbcnt_lo_u32_b32 %0, -1, 0\n\tv_mbcnt_hi_u32_b32 %0, -1, %0" : "=v"(lane));
     screen_select_store<8, 512, true, 0, POOL, RUN, F16, EPI>(acc4, wf, sc.nw, a2, a3, sets, pm + (size_t)tile * PMW, b4, mb0 * 32,
-                                                         false, valid, tile, sc, lane, 512, frun, first, F16 ? sa : 0);
+                                                         false, valid, tile, sc, lane, 512, frun, first, F16 ? sa : 0,
+                                                         F16 ? rho : 0x1p-11f);
   }
 };
 typedef Trunk4ScreenT<false> Trunk4Screen;
@@ -1203,7 +1316,8 @@ template <bool F16>
 using StnPipeT = typename ScreenPipeSel<F16, StnScreenPipeF16, StnScreenPipe>::type;
 
 // scratch: LDS that is dead after conv2 (a1 / h1, 34 KiB): [0, 128) the row norms of both tiles, from float 128 on the
-// waves' candidate sets (4 x 4 KiB).  g holds the first sweep's first weight fragments (requested in front of conv2).
+// waves' candidate sets (4 x 4 KiB), behind them [4224, 4352) the rows' rho (`screen_da`).  img is written behind ReLU
+// (store_tile_lds_pre<1, 4, RELU = true> of both callers): no negative element, which the sign-split dws needs.  g holds the first sweep's first weight fragments (requested in front of conv2).
 // probe_rows (tests only): the image rows as [tile][64][128]
 // RUN: the run form (k_stn*_pair_sr) - frun = the 1024 running maxima of the run (LDS, -inf in front of the first tile;
 // first_pair: they are not to be read)
@@ -1214,13 +1328,17 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
                                                    float* __restrict__ probe_rows, int wave, int tid, int lane,
                                                    float* frun = nullptr, bool first_pair = true) {
   const int nt = valid2 > TP ? 2 : 1, mb0 = wave * 8;
-  screen_row_norms<128, 256, 2 * TP, false>(img, scratch, tid, LD128);
+  const bool da = F16 && sc.da != 0;
+  float* rho = scratch + 2 * TP + 4 * 1024;
+  SCREEN_STAMP(LAYER, tile0, wave, 6);  // [6] .. [7]: the row norms (with `screen_da`: and the measuring) of both tiles
+  screen_row_norms<128, 256, 2 * TP, false>(img, scratch, tid, LD128, da, rho);
   if (probe_rows) {
     for (int i = tid; i < nt * TP * 32; i += 256)
       *reinterpret_cast<f32x4*>(probe_rows + ((size_t)tile0 * TP + (i >> 5)) * 128 + (i & 31) * 4) =
           *reinterpret_cast<const f32x4*>(img + (i >> 5) * LD128 + (i & 31) * 4);
   }
   __syncthreads();
+  SCREEN_STAMP(LAYER, tile0, wave, 7);
   unsigned long long* sets = reinterpret_cast<unsigned long long*>(scratch + 2 * TP) + wave * 8 * 64;
   // The two tiles one after the other on the same accumulators, as two copies of the code: in a runtime loop the compiler
   // hoists the selection's ~25 bit-mask constants and the lane-dependent addresses out of it, across the sweep, and spills.
@@ -1230,8 +1348,10 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
     for (int mb = 0; mb < 8; ++mb) acc[mb][0] = acc[mb][1] = zero16();
     const float* x = img + t * TP * LD128;
     int sa = 0;
+    float rho_t = 0x1p-11f;
     if constexpr (F16) {
       sa = screen_tile_scale(scratch + t * TP, ln);
+      rho_t = screen_tile_rho(rho + t * TP, ln, da);
       g.run(acc, x, ln, sa);
     } else {
       g.run(acc, x, ln);
@@ -1242,7 +1362,7 @@ __device__ __forceinline__ void stn_conv3_screened(const float* img, float* scra
     screen_select_store<8, 128, false, LAYER, POOL, RUN, F16, EPI>(acc, wf, sc.nw, scratch + t * TP, x, sets,
                                                               pm + (size_t)(tile0 + t) * PMW, b3, mb0 * 32, true,
                                                               min(valid2 - t * TP, TP), tile0 + t, sc, ln, LD128, frun,
-                                                              first_pair && t == 0, sa);
+                                                              first_pair && t == 0, sa, rho_t);
   };
   tile(0, lane);
   if (nt == 2) {  // (again a fresh lane id: nothing lane-dependent of the first tile stays live across its epilogue)
@@ -1408,6 +1528,7 @@ struct Stn3dRunArgs {
   const float* nw;
   int B, N, M, SP;
   const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
+  int da;           // ... and its `screen_da` (ScreenArgs::da)
 };
 
 template <bool F16, bool EPI = false>
@@ -1428,7 +1549,7 @@ __device__ __forceinline__ void stn3d_pair_sr_body() {
     asm volatile("" : "+s"(ap));
     const Stn3dRunArgs a = *(const Stn3dRunArgs*)ap;
     stn3d_pair_s_body<true, true, F16, EPI>(a.P, a.W1, a.b1, a.wp2, a.b2, a.wp3, a.b3, a.pm, a.B, a.N, a.M,
-                                       ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane, frun,
+                                       ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw, a.da}, nullptr, bid, wave * 64 + lane, frun,
                                        false);
     __syncthreads();  // the next pair's conv1 overwrites the candidate sets, its conv2 the image the other waves replay from
   }
@@ -1460,6 +1581,7 @@ struct StnkdRunArgs {
   const float* nw;
   int B, N, M, SP;
   const float* uw;  // fp16 screen (k_stn*_pair_sr16; wps then are its fragments)
+  int da;           // ... and its `screen_da` (ScreenArgs::da)
 };
 
 template <bool F16, bool EPI = false>
@@ -1480,7 +1602,7 @@ __device__ __forceinline__ void stnkd_pair_sr_body() {
     asm volatile("" : "+s"(ap));
     const StnkdRunArgs a = *(const StnkdRunArgs*)ap;
     stnkd_pair_s_body<true, true, F16, EPI>(a.P, a.trans3, a.Wc1, a.bc1, a.wpf1, a.bf1, a.wpf2, a.bf2, a.wpf3, a.bf3, a.pm, a.B, a.N,
-                                       a.M, ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw}, nullptr, bid, wave * 64 + lane,
+                                       a.M, ScreenArgs{a.wps, a.nw, nullptr, nullptr, a.uw, a.da}, nullptr, bid, wave * 64 + lane,
                                        frun, false);
     __syncthreads();
   }

@@ -309,7 +309,10 @@ def bump_param_epoch():
 FORM_IDS = {"trunk4": 0, "stn4": 1, "stn_pair": 2, "rotw": 3, "fc_tail": 4, "screen": 5, "screen_stn": 6, "screen_pool": 7,
             "screen_run": 8, "screen_f16": 9,
             # no bit of the form word (ids 10 - 12 are the raw bits of the env-only STN arms): the epilogue of the `screen_f16` kernels
-            "screen_epi": 13}
+            "screen_epi": 13,
+            # likewise no bits of the form word: the bound the `screen_f16` kernels select with (eps from the measured
+            # activation rounding and the sign-split weight error), and its arm for the two STN kernels
+            "screen_da": 14, "screen_da_stn": 15}
 
 
 def form_switch(name, value=None):

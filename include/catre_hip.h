@@ -356,6 +356,12 @@ int catre_profile_enable(int kernel_id, int max_records);
  * the carry, the wave prefix on the DPP path, one scan loop - k_trunk4sr16e / k_trunk4sp16e and the four STN kernels of the
  * same suffix; the same candidates and the same bits.  No form of its own (catre_form_decision does not read it); these
  * kernels carry no probe code, a probe call takes the kernels of 9 (the trunk's: the one-tile kernel), default on,
+ * 14 (`screen_da`, CATRE_SCREEN_DA = 0) and 15 (`screen_da_stn`, CATRE_SCREEN_DA_STN = 1; it counts while 14 is on): the
+ * error bound the fp16-screen kernels of 9 and 13 select with takes the activations' fp16 rounding as MEASURED per tile
+ * (in the pass that takes the row norms) instead of its worst case, and the weights' rounding error split by sign (the
+ * screened layers read post-ReLU images) - a runtime flag of the same kernels, no form and no kernel of its own; fewer
+ * candidates reach the fp32 replay, the outputs keep their bits; 14 is the trunk's conv4, 15 the two STN kernels' conv3;
+ * both probes follow them and return the bound in use,
  * `value` 1 / 0 sets it, value < 0 only queries.  Returns
  * the PREVIOUS setting (1 / 0), -1 for an unknown id.  Process-wide (an atomic word; defaults: 0-2 and 5-9 on, 3 and 4 off -
  * they measured slower - or what the environment says: CATRE_TRUNK4 / CATRE_STN4 / CATRE_STN_PAIR / CATRE_SCREEN /
