@@ -786,6 +786,14 @@ int catre_op_pad_cols(const float* src, long stride_row, long stride_col, int ro
   return check_launch();
 }
 
+// 64-row tiles of one cloud a workgroup of k_cloud_matmul64 takes: 4 once that still leaves >= 4 workgroups per CU, else 1
+// (a pure host function: the launch below calls it, tests ask it which route a shape takes); -1 for sizes no launch accepts
+int catre_op_cloud_matmul_tpw(int B, int N, int M) {
+  if (B <= 0 || N <= 0 || M < 0) return -1;
+  const int C = M > 0 ? 2 * B : B, maxn = N > M ? N : M, tiles = (maxn + 63) / 64;
+  return (tiles >= 4 && (size_t)C * (tiles / 4) >= 1024) ? 4 : 1;
+}
+
 // Y[r][:] = X[r][:] T[cloud(r)] (or T^T), kd in {3, 64}; rows cloud-major
 int catre_op_cloud_matmul(const float* X, int ldx, const float* T, float* Y, int ldy, int kd, int B, int N, int M,
                           int transpose, void* stream) {
@@ -796,8 +804,7 @@ int catre_op_cloud_matmul(const float* X, int ldx, const float* T, float* Y, int
     hipLaunchKernelGGL((k_cloud_matmul<3>), grid, dim3(256), 0, (hipStream_t)stream, X, ldx, T, Y, ldy, R, B, N, M,
                        transpose);
   else if ((ldx % 4) == 0 && (ldy % 4) == 0) {
-    // tiles per workgroup: 4 once that still leaves >= 4 workgroups per CU
-    const int tiles = (maxn + 63) / 64, tpw = (tiles >= 4 && (size_t)C * (tiles / 4) >= 1024) ? 4 : 1;
+    const int tiles = (maxn + 63) / 64, tpw = catre_op_cloud_matmul_tpw(B, N, M);
     hipLaunchKernelGGL(k_cloud_matmul64, dim3((tiles + tpw - 1) / tpw, C), dim3(256), 0, (hipStream_t)stream, X, ldx, T, Y,
                        ldy, B, N, M, transpose, tpw);
   }

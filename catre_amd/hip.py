@@ -185,6 +185,7 @@ _SIGS = {
     "catre_op_maxlin_bwd_x": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _P]),
     "catre_op_maxlin_bwd_x_rows": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P]),
     "catre_op_cloud_matmul": (_I, [_P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
+    "catre_op_cloud_matmul_tpw": (_I, [_I, _I, _I]),
     "catre_op_cloud_matmul_bwd_t": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _P]),
     "catre_op_relu_bwd": (_I, [_P, _P, _P, _SZ, _P]),
     "catre_op_sum_rows": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P]),
@@ -333,6 +334,15 @@ def screen_run_len(value=None):
 def screen_run_rule(B, N, M, cus=256):
     """The run length the library's rule picks for a (B, N, M) grid on `cus` compute units (a pure host function)."""
     return load().catre_screen_run_rule(B, N, M, cus)
+
+
+def cloud_matmul_tpw(B, N, M):
+    """The 64-row tiles of one cloud a workgroup of the kd = 64 ``catre_op_cloud_matmul`` launch takes (4 or 1) for a
+    (B, N, M) batch: a pure host function of the library, the one the launch calls."""
+    r = load().catre_op_cloud_matmul_tpw(B, N, M)
+    if r < 0:
+        raise CatreHipError(f"catre_op_cloud_matmul_tpw: no launch takes B, N, M = {B}, {N}, {M}")
+    return r
 
 
 # catre_kernel_form, in the order the launches try them

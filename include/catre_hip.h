@@ -517,6 +517,9 @@ int catre_op_maxlin_bwd_x_rows(const float* dg, const int* idx, const float* W, 
                                int B, int N, int M, void* stream);
 int catre_op_cloud_matmul(const float* X, int ldx, const float* T, float* Y, int ldy, int kd, int B, int N, int M,
                           int transpose, void* stream);
+/* the 64-row tiles of one cloud a workgroup of the kd = 64 launch above takes (4 or 1): a pure host function, the rule the
+ * launch itself calls; -1 for sizes it refuses */
+int catre_op_cloud_matmul_tpw(int B, int N, int M);
 int catre_op_cloud_matmul_bwd_t(const float* X, int ldx, const float* dY, int ldy, float* dT, int kd, int B, int N,
                                 int M, void* stream);
 /* out[R,K] = a + b + (c on its first Rc rows): a, b [R,K] contiguous, c [Rc,K] with leading dimension ldc, each optional
