@@ -258,6 +258,31 @@ def test_the_shapes_sit_on_both_sides_of_every_threshold():
     assert seen == set(hip.KERNEL_FORMS)                                   # every form is reached
 
 
+def test_the_shapes_of_the_training_encoder_forward_test_take_the_forms_it_names():
+    """The (mode, B, N, M) rows of tests/test_train_encoder_fwd.py, which checks the SAVE kernels form by form on the GPU
+    and asserts these same decisions there: a threshold that moves fails here first, and names the GPU cases to re-shape."""
+    form = lambda stage, mode, B, N, M, raw=DEFAULTS, rows=True: hip.form_decision(stage, mode, B, N, M, raw, save=True, rows=rows,
+                                                                                  bf_pair_min=512)[0]
+    all3 = lambda mode, B, N, M, raw=DEFAULTS, rows=True: tuple(form(s, mode, B, N, M, raw, rows or s == "trunk")
+                                                                for s in ("stn3d", "stnkd", "trunk"))
+    # fp32, rows saved: the smallest grids; 132 tiles, with and without the one-wave-per-SIMD trunk
+    assert all3("fp32", 1, 64, 64) == all3("fp32", 2, 192, 64) == ("train_rs1",) * 3
+    assert all3("fp32", 33, 128, 128) == ("train_rs1", "train_rs1", "train_wave4")
+    assert all3("fp32", 33, 128, 128, raw=DEFAULTS & ~(1 << TRUNK4)) == ("train_rs1",) * 3
+    # fp32, STN rows not saved: below the pair threshold, and 256 pairs of an odd tile count with and without `stn_pair`
+    assert all3("fp32", 2, 192, 64, rows=False) == ("train_rs1",) * 3
+    assert stn_pairs(64, 192, 192) == 256 and (192 // TP) % 2 == 1
+    assert all3("fp32", 64, 192, 192, rows=False) == ("train_pair", "train_pair", "train_wave4")
+    assert all3("fp32", 64, 192, 192, rows=False, raw=DEFAULTS & ~(1 << STN_PAIR)) == ("train_rs1", "train_rs1", "train_wave4")
+    assert all3("fp32", 64, 192, 192) == ("train_rs1", "train_rs1", "train_wave4")
+    assert all3("split", 2, 192, 64) == all3("split", 33, 128, 128) == ("train_split",) * 3
+    # bf16: one-tile STN kernels next to the trunk's pair kernel; 512 pairs
+    assert all3("bf16", 2, 192, 64) == ("train_bf", "train_bf", "train_bf_pair")
+    assert stn_pairs(128, 192, 192) == 512 and all3("bf16", 128, 192, 192) == ("train_bf_pair",) * 3
+    # the B = 3 batches its batch-independence cases run next to the large grids
+    assert all3("bf16", 3, 192, 192) == ("train_bf", "train_bf", "train_bf_pair") and all3("fp32", 3, 128, 128) == ("train_rs1",) * 3
+
+
 def test_nonsense_is_refused():
     decide = _decide()
     ok = (0, 0, 0, 0, 0, 4, 64, 64, DEFAULTS, 256, 0, 512)
