@@ -1,5 +1,6 @@
 // catre_extras.hip - the unit of libcatre_hip.so around the refine path: train-time augmentation and init noise, point-cloud
-// preparation (per image and per frame batch), NOCS alignment, tracking, trimmed ICP, the splat render, the BOP pose errors,
+// preparation (per image and per frame batch), NOCS alignment, tracking, trimmed ICP, the splat render, the mesh rasteriser, the
+// BOP pose errors,
 // the training loss and the device evaluator, each as a kernel header and its C ABI beside it.
 #include <algorithm>
 #include <cstring>
@@ -11,6 +12,7 @@
 #include "catre_track.h"
 #include "catre_icp.h"
 #include "catre_render.h"
+#include "catre_mesh.h"
 #include "catre_bop.h"
 #include "catre_loss.h"
 #include "catre_eval.h"
@@ -26,6 +28,7 @@ extern "C" {
 #include "catre_track_api.inc"
 #include "catre_icp_api.inc"
 #include "catre_render_api.inc"
+#include "catre_mesh_api.inc"
 #include "catre_bop_api.inc"
 #include "catre_loss_api.inc"
 #include "catre_eval_api.inc"

@@ -260,6 +260,9 @@ _SIGS = {
     # splat render of the posed prior (include/catre_hip.h "splat render of the posed prior", catre_amd/render.py)
     "catre_splat_workspace_bytes": (_SZ, [_I, _I, _I]),
     "catre_splat_render": (_I, [_P] * 7 + [ctypes.c_float, ctypes.c_float] + [_I] * 5 + [_P, _SZ] + [_P] * 8),
+    # mesh rasteriser (include/catre_hip.h "rasteriser of posed triangle meshes", catre_amd/render.py render_mesh)
+    "catre_mesh_workspace_bytes": (_SZ, [_I, _I, _I, _I]),
+    "catre_mesh_render": (_I, [_P] * 12 + [ctypes.c_float] + [_I] * 10 + [_P, _SZ] + [_P] * 10),
     # BOP pose errors (include/catre_hip.h "BOP pose errors: MSSD, MSPD, proj_sym and VSD", catre_amd/pose_errors.py)
     "catre_sym_err_workspace_bytes": (_SZ, [_I, _I]),
     "catre_sym_err": (_I, [_P, _I, _I] + [_P] * 8 + [_I] * 4 + [_P, _SZ] + [_P] * 4),

@@ -8,6 +8,7 @@
 * :func:`sym_errors` - MSSD, MSPD and proj_sym with the winning symmetry of each.
 * :func:`vsd` - visible surface discrepancy of two rendered depth images against an observed one, from ANY renderer.
 * :func:`vsd_prior` - two ``render.splat_prior`` calls and :func:`vsd`: the VSD of the splatted point prior.
+* :func:`vsd_mesh` - two ``render.render_mesh`` calls and :func:`vsd`: the VSD of the rasterised model mesh, BOP's own.
 
 Everything is bit-reproducible: the maxima and minima do not depend on an order, the mean is a fixed tree, the VSD counts
 are integer sums.  An instance's results do not depend on the batch around it.  A NaN in a pose, scale or point makes the
@@ -407,5 +408,50 @@ def vsd_prior(kps, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_
     _frames(frame_of, I, 1 if depth_test.ndim == 2 else depth_test.shape[0], depth_test.device)
     est = render.splat_prior(kps, pose_est, scale_est, Kw, size, frame_of=own, n_frames=I, rho_rel=rho_rel, r_max=r_max, rho=rho)
     gt = render.splat_prior(kps, pose_gt, scale_gt, Kw, size, frame_of=own, n_frames=I, rho_rel=rho_rel, r_max=r_max, rho=rho)
+    return vsd(est.zbuf, gt.zbuf, depth_test, Kh, delta=delta, taus=taus, diameter=diameter, frame_of=frame_of, origin=origin,
+               visib_mode=visib_mode)
+
+
+def vsd_mesh(meshes, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of=None, origin=None, size=None,
+             pixel_center=0.0, delta=0.015, taus=DEFAULT_TAUS, diameter=None, visib_mode="bop19"):
+    """VSD of the RASTERISED MODEL MESH, as BOP defines it -> (errors [I,T] fp64, counts [I,2+T] int32): two
+    ``render.render_mesh`` calls - the meshes (a ``meshes.MeshSet`` of I instances) at (pose_est, scale_est) and at (pose_gt,
+    scale_gt) - and :func:`vsd` on their depth images.
+
+    Every instance is rendered into a frame of its own - no object occludes another, as BOP renders them; occlusion BETWEEN
+    the instances of a scene is therefore not part of the error (it enters through ``depth_test`` alone).  ``size`` = (h, w) and
+    ``origin`` [I,2] = (u0, v0) (a list, needed on the host) render a window of the frame instead of all of it, with the same
+    windowed camera as :func:`vsd_prior`: K with ``cx - u0``, ``cy - v0`` (fp32); :func:`vsd` gets the full-image K.
+    ``pixel_center``: as ``render_mesh``; :func:`vsd` back-projects an integer pixel as its own centre, which is what 0.0
+    renders.  K [3,3] or [I,3,3] is read on the host.  Everything either render or the comparison would refuse is refused
+    before the device is touched; the ABI-call count is constant."""
+    from . import render
+
+    if not isinstance(pose_est, torch.Tensor) or pose_est.ndim != 3:
+        raise ValueError("pose_est: expected a [I,3,4] tensor")
+    I = pose_est.shape[0]
+    if not isinstance(depth_test, torch.Tensor) or depth_test.ndim not in (2, 3):
+        raise ValueError("depth_test: expected a [F,H,W] or [H,W] tensor")
+    if size is None:
+        if origin is not None:
+            raise ValueError("origin needs size = (h, w), the window it places")
+        size = tuple(depth_test.shape[-2:])
+    Kh = torch.as_tensor(K, dtype=torch.float32).cpu()
+    if tuple(Kh.shape) not in ((3, 3), (I, 3, 3)):
+        raise ValueError(f"K must be [3,3] or [{I},3,3], got {tuple(Kh.shape)}")
+    Kw = Kh.expand(I, 3, 3).clone()
+    if origin is not None:
+        o = _origins(origin, I, torch.device("cpu"))().float()
+        Kw[:, 0, 2] -= o[:, 0]
+        Kw[:, 1, 2] -= o[:, 1]
+    own = list(range(I))
+    _vsd_options(taus, visib_mode, "step")
+    if delta != delta:
+        raise ValueError("delta is NaN")
+    for pose, scale in ((pose_est, scale_est), (pose_gt, scale_gt)):
+        render._check_mesh_args(meshes, pose, scale, Kw, size, own, I, None, pixel_center)
+    _frames(frame_of, I, 1 if depth_test.ndim == 2 else depth_test.shape[0], depth_test.device)
+    est = render.render_mesh(meshes, pose_est, scale_est, Kw, size, frame_of=own, n_frames=I, pixel_center=pixel_center)
+    gt = render.render_mesh(meshes, pose_gt, scale_gt, Kw, size, frame_of=own, n_frames=I, pixel_center=pixel_center)
     return vsd(est.zbuf, gt.zbuf, depth_test, Kh, delta=delta, taus=taus, diameter=diameter, frame_of=frame_of, origin=origin,
                visib_mode=visib_mode)

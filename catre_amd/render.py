@@ -18,6 +18,7 @@ bit-reproducible, and a frame's outputs do not depend on the other frames of the
 import ctypes
 from collections import namedtuple
 
+import numpy as np
 import torch
 
 from . import hip, tracking
@@ -148,3 +149,114 @@ def fit_score_visible(pcl, kps, pose, scale, K, depth, tau_rel=0.1, rho_rel=0.06
     d = torch.where(vis, torch.sqrt(nn.nn_d2).double(), torch.zeros((), dtype=torch.float64, device=vis.device)).sum(dim=1)
     d_vis = (d / n_vis.double()).float()          # 0 / 0 = NaN: no visible point
     return score, d_vis, n_vis.float() / vis.shape[1]
+
+
+# ---- mesh rasteriser ---------------------------------------------------------------------------------------------------------
+ABI_CALLS.update({"catre_mesh_workspace_bytes": 0, "catre_mesh_render": 0})
+
+MeshRender = namedtuple("MeshRender", "labels zbuf face cls labels_fit counts culled coord projected")
+
+
+def _check_mesh_args(meshes, poses, scales, K, size, frame_of, n_frames, depth, pixel_center=0.0):
+    """Everything :func:`render_mesh` refuses (``ValueError``), before the device is touched ->
+    (I, F, H, W, frame_of list, K [F,3,3] on the host, pixel_center_half, inst_vert_off, inst_face_off).
+    ``pose_errors.vsd_mesh`` calls this too, to refuse both of its renders before the first."""
+    from .meshes import MeshSet
+
+    if not isinstance(meshes, MeshSet):
+        raise ValueError(f"meshes: expected a MeshSet, got {type(meshes).__name__}")
+    I = meshes.n_inst
+    if tracking._opt(poses, "poses", (I, 3, 4)) is None or tracking._opt(scales, "scales", (I, 3)) is None:
+        raise ValueError("render_mesh needs poses [I,3,4] and scales [I,3]")
+    if pixel_center not in (0.0, 0.5):
+        raise ValueError(f"pixel_center must be 0.0 (an integer pixel is its own centre) or 0.5, got {pixel_center!r}")
+    try:
+        H, W = (int(v) for v in size)
+    except (TypeError, ValueError):
+        raise ValueError(f"size must be (H, W), got {size!r}") from None
+    F = int(n_frames)
+    if H < 1 or W < 1 or F < 1:
+        raise ValueError(f"size and n_frames must be positive, got {(H, W)} and {F}")
+    if F * H * W >= 2 ** 30:
+        raise ValueError(f"{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)")
+    if depth is not None and (not isinstance(depth, torch.Tensor) or tuple(depth.shape) not in ((F, H, W), (H, W))
+                              or (depth.ndim == 2 and F != 1)):
+        raise ValueError(f"depth must be [{F},{H},{W}], got {tuple(getattr(depth, 'shape', ()))}")
+    fo = [0] * I if frame_of is None else [int(v) for v in (frame_of.tolist() if hasattr(frame_of, "tolist") else frame_of)]
+    if len(fo) != I:
+        raise ValueError(f"frame_of holds {len(fo)} frames for {I} instances")
+    for i, f in enumerate(fo):
+        if not 0 <= f < F:
+            raise ValueError(f"frame_of[{i}] = {f} is outside the {F} frames")
+    Kt = torch.as_tensor(K, dtype=torch.float32).cpu()
+    if tuple(Kt.shape) == (3, 3):
+        Kt = Kt.expand(F, 3, 3)
+    elif tuple(Kt.shape) != (F, 3, 3):
+        raise ValueError(f"K must be [3,3] or [{F},3,3], got {tuple(Kt.shape)}")
+    ivo, ifo = meshes.instance_offsets()
+    if ivo[-1] >= 2 ** 31 or ifo[-1] >= 2 ** 31:
+        raise ValueError(f"{int(ivo[-1])} posed vertices and {int(ifo[-1])} posed faces: both must stay below 2^31")
+    for t, name in ((poses, "poses"), (scales, "scales"), (depth, "depth")):
+        if t is not None and t.device != meshes.device:
+            raise ValueError(f"{name} is on {t.device}, the meshes on {meshes.device}")
+    return I, F, H, W, fo, Kt, int(pixel_center == 0.5), ivo, ifo
+
+
+def render_mesh(meshes, poses, scales, K, size, frame_of=None, n_frames=1, depth=None, delta=0.015, pixel_center=0.0,
+                return_coords=False, return_projected=False):
+    """Rasterise I posed triangle meshes into ``n_frames`` images of ``size = (H, W)`` -> ``MeshRender``.
+
+    meshes: a ``meshes.MeshSet`` on the device (instance i draws mesh ``mesh_of[i]``); poses [I,3,4], scales [I,3]: fp32 on
+    the device, a vertex stands at ``R (s * x) + t``.  K [3,3] or [F,3,3] (read on the host); ``frame_of`` [I] (list / CPU
+    tensor; None: frame 0); ``depth`` [F,H,W] fp32 metres on the device, or None; ``delta``: the tolerance of the
+    visibility test, as in :func:`splat_prior`.  ``pixel_center``: 0.0 - an integer pixel is its own centre, the convention of
+    :func:`splat_prior` and ``pcl_prep`` - or 0.5 - pixel (px, py) is sampled at (px + 0.5, py + 0.5), where the GL
+    renderers of ``lib/pysixd`` sample; anything else raises ``ValueError``.
+
+    Vertices are projected like the splat's points and snapped to 1/256 pixel; coverage is exact integer arithmetic on the
+    snapped corners with the top-left fill rule (a sample on an edge shared by two faces belongs to exactly one), depth is
+    perspective-correct in fp64; the nearest depth wins a pixel, then the lower instance, then the lower face.  There is NO
+    clipping: a face with a vertex at or behind the camera plane (or with an index outside its mesh) is culled whole and
+    counted in ``culled``.  The full contract stands at ``catre_mesh_render`` in ``include/catre_hip.h``.
+
+    ``MeshRender``: labels [F,H,W] int32 (i + 1, 0 = background), zbuf [F,H,W] fp32 (0 = background), face [F,H,W] int32 (the
+    winning face's index in its mesh, -1), cls [F,H,W] uint8, labels_fit [F,H,W] int32 and counts [I,5] int32 as ``Splat``
+    has them, culled [I] int32; with ``return_coords`` coord [F,H,W,3] fp32, the model-space point (unposed, unscaled) under
+    the pixel, 0 on background - for a NOCS-normalised model its NOCS map minus the 0.5 offset; with ``return_projected``
+    projected [NV,4] int32, the vertex records (xi, yi, bits of z, ok) instance-major.  ``labels`` / ``labels_fit`` have the form
+    ``pcl_prep.sample_frames(labels=..., label_of=[1..I])`` consumes, ``zbuf`` is a depth image for it, for
+    ``nocs_align.init_from_frames`` (with ``coord + 0.5``) and for ``pose_errors.vsd``.  Everything is bit-reproducible, and a
+    frame's outputs do not depend on the other frames of the call.  Arguments are checked (``ValueError``) before the device
+    is touched; nothing is copied back to the host; the number of ABI calls is constant."""
+    if delta != delta:
+        raise ValueError("delta is NaN")
+    I, F, H, W, fo, Kt, half, ivo, ifo = _check_mesh_args(meshes, poses, scales, K, size, frame_of, n_frames, depth, pixel_center)
+    lib = hip.load()
+    poses = hip.require_dev_f32(poses, "poses", contiguous=False).contiguous()
+    dev = poses.device
+    scales = hip.require_dev_f32(scales, "scales", contiguous=False).contiguous()
+    if depth is not None:
+        depth = hip.require_dev_f32(depth, "depth", contiguous=False).contiguous()
+    NV, NF = int(ivo[-1]), int(ifo[-1])
+    off = torch.from_numpy(np.stack([ivo, ifo]).astype(np.int32)).to(dev, non_blocking=True)
+    ABI_CALLS["catre_mesh_workspace_bytes"] += 1
+    nbytes = lib.catre_mesh_workspace_bytes(F, H, W, NV)
+    if nbytes == 0:
+        raise ValueError(f"{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)")
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    labels, face, labels_fit, counts, culled = i32(F, H, W), i32(F, H, W), i32(F, H, W), i32(I, 5), i32(I)
+    zbuf = torch.empty(F, H, W, dtype=torch.float32, device=dev)
+    cls = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    coord = torch.empty(F, H, W, 3, dtype=torch.float32, device=dev) if return_coords else None
+    projected = i32(NV, 4) if return_projected else None
+    k9 = (ctypes.c_float * (9 * F))(*[float(v) for v in Kt.reshape(-1)])
+    fo_c = (ctypes.c_int32 * I)(*fo)
+    ABI_CALLS["catre_mesh_render"] += 1
+    hip.check(lib.catre_mesh_render(hip.ptr(meshes.verts), hip.ptr(meshes.faces), hip.ptr(meshes.vert_off), hip.ptr(meshes.face_off),
+                                    hip.ptr(meshes.mesh_of), hip.ptr(off[0]), hip.ptr(off[1]), hip.ptr(poses), hip.ptr(scales),
+                                    hip.ptr(depth), k9, fo_c, float(delta), half, meshes.n_meshes, meshes.v_tot, meshes.t_tot, F, I,
+                                    NV, NF, H, W, hip.ptr(ws), nbytes, hip.ptr(labels), hip.ptr(zbuf), hip.ptr(face), hip.ptr(cls),
+                                    hip.ptr(labels_fit), hip.ptr(counts), hip.ptr(culled), hip.ptr(coord), hip.ptr(projected),
+                                    hip.stream_ptr(dev)), "catre_mesh_render")
+    return MeshRender(labels, zbuf, face, cls, labels_fit, counts, culled, coord, projected)

@@ -1125,6 +1125,55 @@ int catre_splat_render(const float* kps, const float* pose, const float* scale, 
                        void* workspace, size_t ws_bytes, int32_t* labels, float* zbuf, int32_t* point, unsigned char* cls,
                        int32_t* labels_fit, int32_t* counts, unsigned char* vis, void* stream);
 
+/* ---- rasteriser of posed triangle meshes: depth, labels, model coordinates ------------------------------ */
+
+/* catre_mesh_render: the meshes of I instances, posed and projected into the F frames they are seen in, z-buffered per pixel.
+ * The meshes form a ragged table on the device: verts [V_tot,3] fp32, faces [T_tot,3] int32 (indices LOCAL to the mesh),
+ * vert_off, face_off [G+1] int32 (mesh g is rows off[g] .. off[g+1] - 1), mesh_of [I] int32 (the mesh of instance i), and the
+ * instance-major offsets of what is posed: inst_vert_off, inst_face_off [I+1] int32 (running sums of the vertex / face counts
+ * of mesh_of[i]; their last entries are n_posed_vertices and n_posed_faces, both < 2^31).  pose [I,3,4], scale [I,3], depth
+ * [F,H,W] (metres, may be NULL): fp32 on the device.  K = HOST [F][9], frame_of = HOST [I], checked and staged as
+ * catre_splat_render does (one hipMemcpyAsync from pageable memory; nothing is copied back, nothing waits on the device;
+ * the call cannot be captured into a graph because of this copy).  pixel_center_half: 0 = an integer pixel is its own
+ * centre (the convention of catre_splat_render and the point-cloud prep), 1 = pixel (px, py) is sampled at (px + 0.5,
+ * py + 0.5), where the GL renderers of lib/pysixd sample.
+ * Vertices: p = R (s * x) + t (catre_nn_stats' arithmetic); u = fx * p.x / p.z + cx, v = fy * p.y / p.z + cy, each operation
+ * rounded to fp32 in that order; xi = (int)rintf(u * 256), yi likewise (8 fractional bits).  A vertex is ok iff p.z > 0, u
+ * and v are finite and |xi|, |yi| < 2^23.  Everything below is a function of the records (xi, yi, p.z, ok) alone.
+ * Faces: a face with a vertex that is not ok, or with an index outside [0, V_mesh), is culled whole and counted once in
+ * culled[i] - there is no clipping, a face that reaches the camera plane draws nothing - and never indexes out of bounds; a
+ * face of zero doubled area is dropped without being counted.  Either winding draws: the face is oriented so that its
+ * doubled area is positive.  Coverage by int64 edge functions of the snapped corners at the sample (256 px + c, 256 py + c),
+ * c = 0 or 128: strictly inside is covered; a sample exactly on an edge is covered iff the edge is top (horizontal, interior
+ * at larger v) or left (not horizontal, interior at larger u), so a sample on an edge or vertex shared by the faces of a
+ * consistently tessellated surface belongs to exactly one of them.  Depth, perspective-correct, in fp64, every operation
+ * rounded: w_k = (double)E_k * (1.0 / (double)z_k), W = (w_0 + w_1) + w_2, z = (float)((double)area2 / W), E_k the edge function
+ * opposite corner k.  Every covered pixel keeps the minimum of the key (bits(z) << 32) | g, g = inst_face_off[i] + the face's
+ * local index: the nearest depth, then the lower instance, then the lower face.  Integer min does not depend on the order
+ * of arrival: the outputs are bit-reproducible, and a frame's outputs do not depend on the other frames of the call.
+ * Outputs (device; labels, zbuf, counts and culled are required, the others may be NULL):
+ *   labels [F,H,W] int32      i + 1, 0 = background
+ *   zbuf [F,H,W] fp32         the winner's z, 0 = background
+ *   face [F,H,W] int32        the winner's local face index, -1 = background
+ *   cls, labels_fit, counts   as catre_splat_render writes them (CATRE_SPLAT_*, the same constants; counts [I,5])
+ *   culled [I] int32          faces of instance i that were culled
+ *   coord [F,H,W,3] fp32      the model-space point under the pixel, per component (float)(((w_0 a_0 + w_1 a_1) + w_2 a_2) / W)
+ *                             in fp64 with a_k the UNPOSED, UNSCALED vertex coordinate; 0 on background
+ *   projected [NV,4] int32    the vertex records (xi, yi, bits(p.z), ok), instance-major
+ * workspace: catre_mesh_workspace_bytes(F, H, W, n_posed_vertices) bytes of device memory (0 for a size < 1 or
+ * F * H * W >= 2^30).  Four launches on `stream` - clear, project, raster, resolve - the same for any I, F and mesh.
+ * Status, decided before any launch: CATRE_ERR_BAD_ARG (a NULL required array, a size < 1, F * H * W >= 2^30, fewer posed
+ * vertices or faces than instances, delta NaN, pixel_center_half not 0 or 1, frame_of[i] outside [0, F), fx or fy zero or
+ * NaN), CATRE_ERR_UNSUPPORTED (I > 2^27), CATRE_ERR_WORKSPACE (workspace NULL or short). */
+size_t catre_mesh_workspace_bytes(int F, int H, int W, int n_posed_vertices);
+int catre_mesh_render(const float* verts, const int32_t* faces, const int32_t* vert_off, const int32_t* face_off,
+                      const int32_t* mesh_of, const int32_t* inst_vert_off, const int32_t* inst_face_off, const float* pose,
+                      const float* scale, const float* depth, const float* K, const int32_t* frame_of, float delta,
+                      int pixel_center_half, int G, int V_tot, int T_tot, int F, int I, int n_posed_vertices, int n_posed_faces,
+                      int H, int W, void* workspace, size_t ws_bytes, int32_t* labels, float* zbuf, int32_t* face,
+                      unsigned char* cls, int32_t* labels_fit, int32_t* counts, int32_t* culled, float* coord,
+                      int32_t* projected, void* stream);
+
 /* ---- BOP pose errors: MSSD, MSPD, proj_sym and VSD -------------------------------------------------------- */
 
 /* catre_sym_err: lib/pysixd/pose_error.py mssd (:131-153), mspd (:156-179) and proj_sym (:196-217) of I instances in one
