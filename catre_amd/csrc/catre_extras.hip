@@ -27,6 +27,7 @@ extern "C" {
 #include "catre_align_api.inc"
 #include "catre_track_api.inc"
 #include "catre_icp_api.inc"
+#include "catre_zbuf_api.inc"
 #include "catre_render_api.inc"
 #include "catre_mesh_api.inc"
 #include "catre_bop_api.inc"

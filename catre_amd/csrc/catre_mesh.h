@@ -1,33 +1,31 @@
 // Rasteriser of posed triangle meshes: every instance's mesh, posed and projected into the frame the instance is seen in,
 // z-buffered per pixel -> instance labels, a depth image, the winning face, a visibility class per pixel against an observed
-// depth (the classes and constants of the splat render, catre_render.h) and, on request, the model-space point under every
-// pixel (for a NOCS-normalised model: its NOCS map minus the 0.5 offset).
+// depth and, on request, the model-space point under every pixel (for a NOCS-normalised model: its NOCS map minus the 0.5
+// offset).  The key image (here bits(z) << 32 | posed face), its tie rule, the classes, the projection, the box walk, the
+// clear kernel (which zeroes `culled` too) and the common part of the resolve are the z-buffer core's (catre_zbuf.h), shared
+// with the splat render; this header holds what is the rasteriser's own.
 //
-// k_mesh_clear     key image := all ones (background), counts := 0, culled := 0.
-// k_mesh_project   one thread per posed vertex (instance-major): R (s * x) + t with nn_load_point, the projection of
-//                  splat_project (product, quotient, sum, each rounded to fp32), snapped to 8 fractional bits
-//                  -> record (xi, yi, bits(z), ok).  From here on everything is a function of the records alone.
+// k_mesh_project   one thread per posed vertex (instance-major): R (s * x) + t with nn_load_point, zbuf_project (the splat's
+//                  projection: one function), snapped to 8 fractional bits -> record (xi, yi, bits(z), ok).  From here on
+//                  everything is a function of the records alone.
 // k_mesh_raster    one LANE sets up one posed face (indices checked, records read, oriented to a positive doubled area, bounding
 //                  box clamped to the image).  Faces whose box holds at most MESH_LANE_PX samples are then drawn by their own
 //                  lanes side by side (a fine mesh: a face is about a pixel, and a wave that walked them one by one would
 //                  leave 60 lanes idle); the WAVE walks the other live faces one after the other with all 64 lanes spread
-//                  over the pixels of the face's box - the scheme of k_splat: boxes run up to the whole image, a thread per
-//                  face would diverge by that factor.  fpw (faces set up per wave, a power of two 4 .. 64) is the host's
+//                  over the pixels of the face's box (zbuf_each_live, zbuf_walk_box).  fpw (faces set up per wave, a power of two 4 .. 64) is the host's
 //                  choice; the image depends neither on it nor on MESH_LANE_PX (integer min of a key that is a function of
 //                  (face, pixel) alone).  Coverage is decided by int64 edge functions of the snapped coordinates - exact -
 //                  with the top-left fill rule; depth is perspective-correct in fp64 from those integers.
-// k_mesh_resolve   one thread per pixel: key -> labels / zbuf / face / class, counts by merged integer atomics, and with
-//                  `coord` the winning face's edge functions again -> the interpolated unposed, unscaled vertex.
+// k_mesh_resolve   one thread per pixel: the core's resolve, the winning face, and with `coord` that face's edge functions
+//                  again -> the interpolated unposed, unscaled vertex.
 //
 // The fp64 arithmetic stands in small functions with contraction off and plain operators: the __dmul_rn / __dadd_rn intrinsics
 // are `*` and `+` of a header compiled with contraction on, and were fused where they met (see bop_dist, catre_bop.h).
 #pragma once
 #include "catre_device.h"
 
-#include "../../include/catre_hip.h"
-#include "catre_pcl.h"
 #include "catre_track.h"
-#include "catre_render.h"
+#include "catre_zbuf.h"
 
 constexpr int MESH_THREADS = 256;
 constexpr int MESH_SNAP = 256;               // sub-pixel positions per pixel
@@ -59,14 +57,6 @@ __device__ __forceinline__ int mesh_owner(const int32_t* __restrict__ off, int n
   return lo;
 }
 
-__global__ __launch_bounds__(256) void k_mesh_clear(unsigned long long* __restrict__ keys, int n, int32_t* __restrict__ counts,
-                                                    int n_counts, int32_t* __restrict__ culled, int n_culled) {
-  const int gi = blockIdx.x * 256 + threadIdx.x;
-  if (gi < n) keys[gi] = SPLAT_BG;
-  if (gi < n_counts) counts[gi] = 0;
-  if (gi < n_culled) culled[gi] = 0;
-}
-
 __global__ __launch_bounds__(256) void k_mesh_project(MeshTables T, const float* __restrict__ pose, const float* __restrict__ scale,
                                                       const int* __restrict__ frame_of, const PclCam* __restrict__ cams,
                                                       int4* __restrict__ rec, int4* __restrict__ rec_out) {
@@ -82,8 +72,8 @@ __global__ __launch_bounds__(256) void k_mesh_project(MeshTables T, const float*
       const PclCam cam = cams[frame_of[i]];
       float x, y, z;
       nn_load_point(T.verts, (size_t)row, pose + (size_t)i * 12, scale + (size_t)i * 3, x, y, z);
-      const float u = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);
-      const float v = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+      float u, v;
+      zbuf_project(cam, x, y, z, u, v);
       const float xs = rintf(__fmul_rn(u, (float)MESH_SNAP)), ys = rintf(__fmul_rn(v, (float)MESH_SNAP));
       // decided in float: a vertex a hair in front of the camera has u beyond any int (a NaN fails every comparison)
       const bool ok = z > 0.f && track_finite(u) && track_finite(v) && fabsf(xs) < MESH_COORD_LIMIT && fabsf(ys) < MESH_COORD_LIMIT;
@@ -172,24 +162,14 @@ __device__ __forceinline__ float mesh_attr(double w0, double w1, double w2, doub
   return (float)q;
 }
 
-__device__ __forceinline__ double mesh_bcast(double v, int j) {
-  const long long b = __double_as_longlong(v);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(b & 0xffffffffll), j);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(b >> 32), j);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
-// one sample of one face: covered -> depth -> key -> atomicMin behind a plain load (min is monotone: a stale value read there
-// only costs an atomic that changes nothing, never a result)
+// one sample of one face: covered -> depth -> key -> zbuf_min
 __device__ __forceinline__ void mesh_shade(int x0, int y0, int x1, int y1, int x2, int y2, double rz0, double rz1, double rz2,
                                            long long area2, unsigned g, unsigned long long* kf, int W, int c256, int px, int py) {
   long long e0, e1, e2;
   if (mesh_cover(x0, y0, x1, y1, x2, y2, px * MESH_SNAP + c256, py * MESH_SNAP + c256, e0, e1, e2)) {
     double w0, w1, w2;
     const double Wn = mesh_weights(e0, e1, e2, rz0, rz1, rz2, w0, w1, w2);
-    const unsigned long long key = ((unsigned long long)(unsigned)__float_as_int(mesh_depth(area2, Wn)) << 32) | g;
-    unsigned long long* p = kf + (size_t)py * W + px;
-    if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
+    zbuf_min(kf + (size_t)py * W + px, zbuf_key(mesh_depth(area2, Wn), g));
   }
 }
 
@@ -238,31 +218,18 @@ __global__ __launch_bounds__(MESH_THREADS) void k_mesh_raster(MeshTables T, cons
     }
     bw = 0;
   }
-  unsigned long long todo = __ballot(bw > 0);
-  while (todo) {
-    const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-    todo &= todo - 1;
-    const int jbx = splat_bcast(bx, j), jby = splat_bcast(by, j), jbw = splat_bcast(bw, j), jbh = splat_bcast(bh, j);
-    const int x0 = splat_bcast(f.x0, j), y0 = splat_bcast(f.y0, j), x1 = splat_bcast(f.x1, j), y1 = splat_bcast(f.y1, j);
-    const int x2 = splat_bcast(f.x2, j), y2 = splat_bcast(f.y2, j);
-    const double jr0 = mesh_bcast(rz0, j), jr1 = mesh_bcast(rz1, j), jr2 = mesh_bcast(rz2, j);
-    const long long area2 = __double_as_longlong(mesh_bcast(__longlong_as_double(f.area2), j));
-    const unsigned jg = (unsigned)splat_bcast((int)gl, j);
-    unsigned long long* kf = keys + (size_t)splat_bcast(frame, j) * H * W;
-    const int total = jbw * jbh;  // <= H * W
-    const int q = 64 / jbw, rem = 64 % jbw;
-    int u = lane % jbw, v = lane / jbw;
-    for (int k = lane; k < total; k += 64) {
-      const int px = jbx + u, py = jby + v;
+  zbuf_each_live(bw > 0, [&](int j) {
+    const int jbx = zbuf_bcast(bx, j), jby = zbuf_bcast(by, j), jbw = zbuf_bcast(bw, j), jbh = zbuf_bcast(bh, j);
+    const int x0 = zbuf_bcast(f.x0, j), y0 = zbuf_bcast(f.y0, j), x1 = zbuf_bcast(f.x1, j), y1 = zbuf_bcast(f.y1, j);
+    const int x2 = zbuf_bcast(f.x2, j), y2 = zbuf_bcast(f.y2, j);
+    const double jr0 = zbuf_bcast(rz0, j), jr1 = zbuf_bcast(rz1, j), jr2 = zbuf_bcast(rz2, j);
+    const long long area2 = zbuf_bcast(f.area2, j);
+    const unsigned jg = (unsigned)zbuf_bcast((int)gl, j);
+    unsigned long long* kf = keys + (size_t)zbuf_bcast(frame, j) * H * W;
+    zbuf_walk_box(lane, jbx, jby, jbw, jbh, [&](int px, int py) {
       mesh_shade(x0, y0, x1, y1, x2, y2, jr0, jr1, jr2, area2, jg, kf, W, c256, px, py);
-      u += rem;
-      v += q;
-      if (u >= jbw) {
-        u -= jbw;
-        ++v;
-      }
-    }
-  }
+    });
+  });
 }
 
 __global__ __launch_bounds__(256) void k_mesh_resolve(MeshTables T, const int4* __restrict__ rec,
@@ -273,22 +240,16 @@ __global__ __launch_bounds__(256) void k_mesh_resolve(MeshTables T, const int4* 
                                                       int32_t* __restrict__ labels_fit, int32_t* __restrict__ counts,
                                                       float* __restrict__ coord) {
   const int gi = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
-  int code = -1;  // instance * 8 + class of a rendered pixel
+  int code = -1;
   if (gi < n) {
     const unsigned long long key = keys[gi];
-    const bool bg = key == SPLAT_BG;
-    const int g = (int)(unsigned)(key & 0xffffffffull);
+    const bool bg = key == ZBUF_BG;
+    const int g = (int)zbuf_key_lo(key);
     const int inst = bg ? 0 : mesh_owner(T.inst_face_off, T.I, g);
     const int local = bg ? -1 : g - T.inst_face_off[inst];
-    const float z = bg ? 0.f : __uint_as_float((unsigned)(key >> 32));
-    const int c = bg ? SPLAT_BACKGROUND : depth ? splat_class(z, depth[gi], delta) : SPLAT_AGREE;
-    const int lab = bg ? 0 : inst + 1;
-    labels[gi] = lab;
-    zbuf[gi] = z;
-    if (face) face[gi] = local;
-    if (cls) cls[gi] = (unsigned char)c;
-    if (labels_fit) labels_fit[gi] = c == SPLAT_AGREE ? lab : 0;
-    if (!bg) code = inst * 8 + c;
+    code = zbuf_resolve_pixel(key, inst, depth, delta, gi, labels, zbuf, cls, labels_fit, [&] {
+      if (face) face[gi] = local;
+    });
     if (coord) {
       float cx = 0.f, cy = 0.f, cz = 0.f;
       MeshFace f;
@@ -308,18 +269,5 @@ __global__ __launch_bounds__(256) void k_mesh_resolve(MeshTables T, const int4* 
       coord[(size_t)gi * 3 + 2] = cz;
     }
   }
-  // neighbouring pixels mostly share (instance, class): one pair of atomics per distinct code of the wave
-  unsigned long long todo = __ballot(code >= 0);
-  while (todo) {
-    const int j = __ffsll((long long)todo) - 1;
-    const int cj = __shfl(code, j);
-    const unsigned long long same = __ballot(code == cj);
-    if (lane == j) {
-      const int cnt = __popcll(same);
-      int32_t* row = counts + (size_t)(cj >> 3) * 5;
-      atomicAdd(row, cnt);
-      atomicAdd(row + (cj & 7), cnt);
-    }
-    todo &= ~same;
-  }
+  zbuf_count(code, lane, counts);
 }

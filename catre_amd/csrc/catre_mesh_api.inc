@@ -1,28 +1,17 @@
-// C ABI of the mesh rasteriser (kernels: catre_mesh.h; declarations: include/catre_hip.h)
+// C ABI of the mesh rasteriser (kernels: catre_mesh.h; shared host side: catre_zbuf_api.inc; declarations: include/catre_hip.h)
 namespace {
 constexpr int MESH_MAX_I = 1 << 27;  // instance * 8 + class is one int in the resolve
-// [F*H*W] 64-bit keys, [NV] vertex records of 16 bytes, then the staged tables: [F] cameras (4 floats each) and frame_of,
-// sized for the most instances NV vertices can belong to (every mesh has a vertex), so that the workspace depends on
-// the frames and the posed vertices alone
+// [F*H*W] 64-bit keys, [NV] vertex records of 16 bytes, then the staged tables with frame_of sized for the most instances NV
+// vertices can belong to (every mesh has a vertex), so that the workspace depends on the frames and the posed vertices alone
 struct MeshWs {
-  size_t keys_bytes, rec_bytes, cams, frame_of, total_bytes;  // cams, frame_of: offsets in ints from the end of the records
+  size_t keys_bytes, rec_bytes, total_bytes;
 };
 inline MeshWs mesh_ws(int F, int H, int W, int NV) {
   MeshWs L;
   L.keys_bytes = align_up((size_t)F * H * W * 8, 16);  // the records are read and written 16 bytes at a time
   L.rec_bytes = (size_t)NV * 16;
-  L.cams = 0;
-  L.frame_of = (size_t)F * 4;
-  L.total_bytes = align_up(L.keys_bytes + L.rec_bytes + (L.frame_of + (size_t)NV) * sizeof(int), 256);
+  L.total_bytes = align_up(L.keys_bytes + L.rec_bytes + zbuf_tab_ints(F, (size_t)NV) * sizeof(int), 256);
   return L;
-}
-// faces set up per wave of k_mesh_raster: 64 where that still gives every SIMD of the chip several waves (4096 in all), fewer -
-// down to 4 - for a handful of small meshes.  The image does not depend on it.
-inline int mesh_fpw(int NF) {
-  const size_t per = (size_t)NF / 4096;
-  int fpw = 4;
-  while (fpw < 64 && (size_t)fpw * 2 <= per) fpw *= 2;
-  return fpw;
 }
 }  // namespace
 
@@ -49,26 +38,16 @@ int catre_mesh_render(const float* verts, const int32_t* faces, const int32_t* v
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* keys = (unsigned long long*)workspace;
   int4* rec = (int4*)((char*)workspace + L.keys_bytes);
-  int* tab = (int*)((char*)workspace + L.keys_bytes + L.rec_bytes);
-  {  // one host->device copy of the tables (pageable source: the runtime has consumed it when the call returns)
-    std::vector<int> head(L.frame_of + I);
-    for (int f = 0; f < F; ++f) {
-      const PclCam cam = pcl_cam(K + f * 9);
-      memcpy(&head[L.cams + (size_t)f * 4], &cam, sizeof cam);
-    }
-    for (int i = 0; i < I; ++i) head[L.frame_of + i] = frame_of[i];
-    if (hipMemcpyAsync(tab, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)
-      return CATRE_ERR_LAUNCH;
-  }
-  const PclCam* cams = (const PclCam*)(tab + L.cams);
-  const int* fo = tab + L.frame_of;
+  ZbufTables tab;
+  if (const int err = zbuf_stage((int*)((char*)workspace + L.keys_bytes + L.rec_bytes), K, frame_of, F, I, st, tab)) return err;
   const MeshTables T{verts, faces, vert_off, face_off, mesh_of, inst_vert_off, inst_face_off, G, V_tot, T_tot, I, NV, NF};
   const int n = F * H * W, c256 = pixel_center_half ? MESH_SNAP / 2 : 0;
-  const int fpw = mesh_fpw(NF), per_block = (MESH_THREADS / 64) * fpw;
-  hipLaunchKernelGGL(k_mesh_clear, dim3((std::max(n, I * 5) + 255) / 256), dim3(256), 0, st, keys, n, counts, I * 5, culled, I);
-  hipLaunchKernelGGL(k_mesh_project, dim3((NV + 255) / 256), dim3(256), 0, st, T, pose, scale, fo, cams, rec, (int4*)projected);
+  const int fpw = zbuf_items_per_wave((size_t)NF), per_block = (MESH_THREADS / 64) * fpw;
+  hipLaunchKernelGGL(k_zbuf_clear, dim3((std::max(n, I * 5) + 255) / 256), dim3(256), 0, st, keys, n, counts, I * 5, culled, I);
+  hipLaunchKernelGGL(k_mesh_project, dim3((NV + 255) / 256), dim3(256), 0, st, T, pose, scale, tab.frame_of, tab.cams, rec,
+                     (int4*)projected);
   hipLaunchKernelGGL(k_mesh_raster, dim3((unsigned)(((long long)NF + per_block - 1) / per_block)), dim3(MESH_THREADS), 0, st, T,
-                     (const int4*)rec, fo, fpw, c256, H, W, keys, culled);
+                     (const int4*)rec, tab.frame_of, fpw, c256, H, W, keys, culled);
   hipLaunchKernelGGL(k_mesh_resolve, dim3((n + 255) / 256), dim3(256), 0, st, T, (const int4*)rec,
                      (const unsigned long long*)keys, depth, delta, n, c256, H, W, labels, zbuf, face, cls, labels_fit, counts,
                      coord);

@@ -1,67 +1,36 @@
 // Splat render of the posed prior: a z-buffered disc splat of every instance's prior points into the frame the instance is
 // seen in -> instance labels, a depth image, the winning point, a visibility class per pixel against an observed depth map
-// (the BOP visibility test, lib/pysixd/visibility.py:9-41, with its visible set split in two) and per-point visibility.
+// and per-point visibility.  The key image, its tie rule, the classes, the projection, the box walk, the clear kernel and
+// the common part of the resolve are the z-buffer core's (catre_zbuf.h); this header holds what is the splat's own.
 //
-// k_splat_clear    key image := all ones (background), counts := 0.
 // k_splat          one workgroup of four waves per (instance, tile of 4 * ppw points).  The first ppw lanes of a wave project
 //                  one point each; the wave then walks its live points one after the other with all 64 lanes spread over the
-//                  pixels of the point's bounding box (footprints vary from 0 to (2 r_max + 1)^2 pixels: a thread per point
-//                  would diverge by that factor).  ppw (a power of two, 4 .. 64) is the host's choice: 64 for a full grid,
-//                  fewer for a handful of objects, whose points then spread over more waves - the walk of a wave is a
-//                  chain of load -> compare -> atomic round trips.  The image does not depend on it (integer min).
-//                  A covered pixel gets atomicMin of the 64-bit key (bits(z) << 32 | instance << 16 | point) - a single
-//                  global_atomic_umin_x2.  Unsigned integer min does not depend on the order of arrival, so the
-//                  image is bit-reproducible; z > 0 makes the fp32 bit pattern order like the value.  A plain load in front
-//                  of the atomic drops it where the pixel already holds a smaller key: min is monotone, so a stale value
-//                  read there only costs an atomic that changes nothing, never a result.
-// k_splat_resolve  one thread per pixel: key -> labels / zbuf / point / class; counts by integer atomics after a wave-level
-//                  merge of equal (instance, class) codes (integer sums: exact in any order).
+//                  pixels of the point's bounding box (footprints vary from 0 to (2 r_max + 1)^2 pixels).  ppw (a power of
+//                  two, 4 .. 64) is the host's choice: 64 for a full grid, fewer for a handful of objects, whose points then
+//                  spread over more waves.  The image does not depend on it (integer min).  A pixel inside the disc gets
+//                  zbuf_min of the key bits(z) << 32 | instance << 16 | point.
+// k_splat_resolve  one thread per pixel: the core's resolve, and the winning point.
 // k_splat_visible  one thread per point: is the point the surface at its centre pixel?
-// The projection is ONE device function (splat_project) for the splat and the visibility launch: same bits.  Every product,
-// quotient and sum in it is spelled with a rounding intrinsic so that nothing is contracted or reordered.
+// The projection is ONE device function (splat_project, around zbuf_project) for the splat and the visibility launch: same bits.
 #pragma once
 #include "catre_device.h"
 
-#include "../../include/catre_hip.h"
-#include "catre_pcl.h"
 #include "catre_track.h"
+#include "catre_zbuf.h"
 
 constexpr int SPLAT_THREADS = 256;
-constexpr unsigned long long SPLAT_BG = ~0ull;
-constexpr int SPLAT_BACKGROUND = CATRE_SPLAT_BACKGROUND, SPLAT_AGREE = CATRE_SPLAT_AGREE, SPLAT_OCCLUDED = CATRE_SPLAT_OCCLUDED,
-              SPLAT_FREE = CATRE_SPLAT_FREE, SPLAT_HOLE = CATRE_SPLAT_HOLE;
 
-// point n of instance data at (pose, scale) -> depth z, centre (u0, v0) in pixels (an integer pixel is its own centre, as
-// in pcl_point) and disc radius r in pixels.  false: the point draws nothing.
+// point n of instance data at (pose, scale) -> depth z, centre (u0, v0) in pixels and disc radius r in pixels.  false: the
+// point draws nothing.
 __device__ __forceinline__ bool splat_project(const float* __restrict__ kps, size_t n, const float* __restrict__ pose,
                                               const float* __restrict__ scale, const PclCam& cam, float rho, float r_max,
                                               float& z, float& u0, float& v0, float& r) {
   float x, y;
   nn_load_point(kps, n, pose, scale, x, y, z);
-  u0 = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fx, x), z), cam.cx);
-  v0 = __fadd_rn(__fdiv_rn(__fmul_rn(cam.fy, y), z), cam.cy);
+  zbuf_project(cam, x, y, z, u0, v0);
   const float rr = __fdiv_rn(__fmul_rn(cam.fx, rho), z);
   r = rr > r_max ? r_max : rr;  // min(rr, r_max) that keeps a NaN rr
   return z > 0.f && track_finite(u0) && track_finite(v0) && track_finite(r);
-}
-
-// observed depth d against rendered depth z
-__device__ __forceinline__ int splat_class(float z, float d, float delta) {
-  if (!(d > 0.f)) return SPLAT_HOLE;
-  const float diff = __fsub_rn(z, d);
-  return diff > delta ? SPLAT_OCCLUDED : diff < -delta ? SPLAT_FREE : SPLAT_AGREE;
-}
-
-__global__ __launch_bounds__(256) void k_splat_clear(unsigned long long* __restrict__ keys, int n, int32_t* __restrict__ counts,
-                                                     int n_counts) {
-  const int gi = blockIdx.x * 256 + threadIdx.x;
-  if (gi < n) keys[gi] = SPLAT_BG;
-  if (gi < n_counts) counts[gi] = 0;
-}
-
-__device__ __forceinline__ int splat_bcast(int v, int j) { return __builtin_amdgcn_readlane(v, j); }
-__device__ __forceinline__ float splat_bcast(float v, int j) {
-  return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), j));
 }
 
 __global__ __launch_bounds__(SPLAT_THREADS) void k_splat(const float* __restrict__ kps, const float* __restrict__ pose,
@@ -96,32 +65,15 @@ __global__ __launch_bounds__(SPLAT_THREADS) void k_splat(const float* __restrict
   }
   unsigned long long* kf = keys + (size_t)frame * H * W;
   const unsigned lo = ((unsigned)inst << 16) | (unsigned)m;
-  unsigned long long todo = __ballot(bw > 0);
-  while (todo) {
-    const int j = __builtin_amdgcn_readfirstlane(__ffsll((long long)todo) - 1);
-    todo &= todo - 1;
-    const int jx0 = splat_bcast(x0, j), jy0 = splat_bcast(y0, j), jbw = splat_bcast(bw, j), jbh = splat_bcast(bh, j);
-    const float ju0 = splat_bcast(u0, j), jv0 = splat_bcast(v0, j), jr2 = splat_bcast(r2, j);
-    const unsigned long long key = ((unsigned long long)(unsigned)splat_bcast(__float_as_int(z), j) << 32) |
-                                   (unsigned)splat_bcast((int)lo, j);
-    const int total = jbw * jbh;  // <= H * W
-    const int q = 64 / jbw, rem = 64 % jbw;
-    int u = lane % jbw, v = lane / jbw;
-    for (int k = lane; k < total; k += 64) {
-      const int px = jx0 + u, py = jy0 + v;
+  zbuf_each_live(bw > 0, [&](int j) {
+    const int jx0 = zbuf_bcast(x0, j), jy0 = zbuf_bcast(y0, j), jbw = zbuf_bcast(bw, j), jbh = zbuf_bcast(bh, j);
+    const float ju0 = zbuf_bcast(u0, j), jv0 = zbuf_bcast(v0, j), jr2 = zbuf_bcast(r2, j);
+    const unsigned long long key = zbuf_key(zbuf_bcast(z, j), (unsigned)zbuf_bcast((int)lo, j));
+    zbuf_walk_box(lane, jx0, jy0, jbw, jbh, [&](int px, int py) {
       const float du = __fsub_rn((float)px, ju0), dv = __fsub_rn((float)py, jv0);
-      if (fmaf(du, du, __fmul_rn(dv, dv)) <= jr2) {
-        unsigned long long* p = kf + (size_t)py * W + px;
-        if (key < __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMin(p, key);
-      }
-      u += rem;
-      v += q;
-      if (u >= jbw) {
-        u -= jbw;
-        ++v;
-      }
-    }
-  }
+      if (fmaf(du, du, __fmul_rn(dv, dv)) <= jr2) zbuf_min(kf + (size_t)py * W + px, key);
+    });
+  });
 }
 
 __global__ __launch_bounds__(256) void k_splat_resolve(const unsigned long long* __restrict__ keys,
@@ -130,35 +82,14 @@ __global__ __launch_bounds__(256) void k_splat_resolve(const unsigned long long*
                                                        int32_t* __restrict__ point, unsigned char* __restrict__ cls,
                                                        int32_t* __restrict__ labels_fit, int32_t* __restrict__ counts) {
   const int gi = blockIdx.x * 256 + threadIdx.x, lane = threadIdx.x & 63;
-  int code = -1;  // instance * 8 + class of a rendered pixel
+  int code = -1;
   if (gi < n) {
     const unsigned long long key = keys[gi];
-    const bool bg = key == SPLAT_BG;
-    const int inst = (int)((key >> 16) & 0xffffu), m = (int)(key & 0xffffu);
-    const float z = bg ? 0.f : __uint_as_float((unsigned)(key >> 32));
-    const int c = bg ? SPLAT_BACKGROUND : depth ? splat_class(z, depth[gi], delta) : SPLAT_AGREE;
-    const int lab = bg ? 0 : inst + 1;
-    labels[gi] = lab;
-    zbuf[gi] = z;
-    if (point) point[gi] = bg ? -1 : m;
-    if (cls) cls[gi] = (unsigned char)c;
-    if (labels_fit) labels_fit[gi] = c == SPLAT_AGREE ? lab : 0;
-    if (!bg) code = inst * 8 + c;
+    code = zbuf_resolve_pixel(key, (int)((key >> 16) & 0xffffu), depth, delta, gi, labels, zbuf, cls, labels_fit, [&] {
+      if (point) point[gi] = key == ZBUF_BG ? -1 : (int)(key & 0xffffu);
+    });
   }
-  // neighbouring pixels mostly share (instance, class): one pair of atomics per distinct code of the wave
-  unsigned long long todo = __ballot(code >= 0);
-  while (todo) {
-    const int j = __ffsll((long long)todo) - 1;
-    const int cj = __shfl(code, j);
-    const unsigned long long same = __ballot(code == cj);
-    if (lane == j) {
-      const int cnt = __popcll(same);
-      int32_t* row = counts + (size_t)(cj >> 3) * 5;
-      atomicAdd(row, cnt);
-      atomicAdd(row + (cj & 7), cnt);
-    }
-    todo &= ~same;
-  }
+  zbuf_count(code, lane, counts);
 }
 
 __global__ __launch_bounds__(256) void k_splat_visible(const float* __restrict__ kps, const float* __restrict__ pose,
@@ -180,7 +111,7 @@ __global__ __launch_bounds__(256) void k_splat_visible(const float* __restrict__
       const size_t pix = ((size_t)frame * H + (int)vc) * W + (int)uc;
       const float zb = zbuf[pix];
       v = labels[pix] == inst + 1 && __fsub_rn(z, zb) <= delta;
-      if (v && depth) v = splat_class(zb, depth[pix], delta) != SPLAT_OCCLUDED;
+      if (v && depth) v = zbuf_class(zb, depth[pix], delta) != SPLAT_OCCLUDED;
     }
   }
   vis[(size_t)inst * M + m] = v ? 1 : 0;

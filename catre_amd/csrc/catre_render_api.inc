@@ -1,30 +1,15 @@
-// C ABI of the splat render (kernels: catre_render.h; declarations: include/catre_hip.h)
+// C ABI of the splat render (kernels: catre_render.h; shared host side: catre_zbuf_api.inc; declarations: include/catre_hip.h)
 namespace {
 constexpr int SPLAT_MAX_I = 65535, SPLAT_MAX_M = 65536;  // 16 bits each in the key; instance 0xffff + point 0xffff never meet all ones (z > 0)
-// pixels are indexed by one int across all frames
-inline bool splat_frames_ok(int F, int H, int W) {
-  return F > 0 && H > 0 && W > 0 && (size_t)F * (size_t)H * (size_t)W < ((size_t)1 << 30);
-}
-// [F*H*W] 64-bit keys, then the staged tables: [F] cameras (4 floats each), [SPLAT_MAX_I] frame_of - sized for any I, so
-// that the workspace depends on the frames alone
+// [F*H*W] 64-bit keys, then the staged tables with frame_of sized for any I, so that the workspace depends on the frames alone
 struct SplatWs {
-  size_t keys_bytes, cams, frame_of, total_bytes;  // cams, frame_of: offsets in ints from the end of the keys
+  size_t keys_bytes, total_bytes;
 };
 inline SplatWs splat_ws(int F, int H, int W) {
   SplatWs L;
   L.keys_bytes = (size_t)F * H * W * 8;
-  L.cams = 0;
-  L.frame_of = (size_t)F * 4;
-  L.total_bytes = align_up(L.keys_bytes + (L.frame_of + SPLAT_MAX_I) * sizeof(int), 256);
+  L.total_bytes = align_up(L.keys_bytes + zbuf_tab_ints(F, SPLAT_MAX_I) * sizeof(int), 256);
   return L;
-}
-// points per wave of k_splat: 64 where that still gives every SIMD of the chip several waves (4096 in all), fewer - down
-// to 4 - for a handful of objects.  The image does not depend on it.
-inline int splat_ppw(int I, int M) {
-  const size_t per = (size_t)I * M / 4096;
-  int ppw = 4;
-  while (ppw < 64 && (size_t)ppw * 2 <= per) ppw *= 2;
-  return ppw;
 }
 }  // namespace
 
@@ -45,28 +30,18 @@ int catre_splat_render(const float* kps, const float* pose, const float* scale, 
   if (!workspace || ws_bytes < L.total_bytes) return CATRE_ERR_WORKSPACE;
   hipStream_t st = (hipStream_t)stream;
   unsigned long long* keys = (unsigned long long*)workspace;
-  int* tab = (int*)((char*)workspace + L.keys_bytes);
-  {  // one host->device copy of the tables (pageable source: the runtime has consumed it when the call returns)
-    std::vector<int> head(L.frame_of + I);
-    for (int f = 0; f < F; ++f) {
-      const PclCam cam = pcl_cam(K + f * 9);
-      memcpy(&head[L.cams + (size_t)f * 4], &cam, sizeof cam);
-    }
-    for (int i = 0; i < I; ++i) head[L.frame_of + i] = frame_of[i];
-    if (hipMemcpyAsync(tab, head.data(), head.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess)
-      return CATRE_ERR_LAUNCH;
-  }
-  const PclCam* cams = (const PclCam*)(tab + L.cams);
-  const int* fo = tab + L.frame_of;
+  ZbufTables tab;
+  if (const int err = zbuf_stage((int*)((char*)workspace + L.keys_bytes), K, frame_of, F, I, st, tab)) return err;
   const int n = F * H * W, tiles = (M + 255) / 256;  // I * tiles <= 65535 * 256
-  const int ppw = splat_ppw(I, M), stiles = (M + 4 * ppw - 1) / (4 * ppw);  // I * stiles <= 65535 * 4096
-  hipLaunchKernelGGL(k_splat_clear, dim3((std::max(n, I * 5) + 255) / 256), dim3(256), 0, st, keys, n, counts, I * 5);
-  hipLaunchKernelGGL(k_splat, dim3(I * stiles), dim3(SPLAT_THREADS), 0, st, kps, pose, scale, rho, fo, cams, M, stiles, ppw, H,
-                     W, r_max, keys);
+  const int ppw = zbuf_items_per_wave((size_t)I * M), stiles = (M + 4 * ppw - 1) / (4 * ppw);  // I * stiles <= 65535 * 4096
+  hipLaunchKernelGGL(k_zbuf_clear, dim3((std::max(n, I * 5) + 255) / 256), dim3(256), 0, st, keys, n, counts, I * 5,
+                     (int32_t*)nullptr, 0);
+  hipLaunchKernelGGL(k_splat, dim3(I * stiles), dim3(SPLAT_THREADS), 0, st, kps, pose, scale, rho, tab.frame_of, tab.cams, M,
+                     stiles, ppw, H, W, r_max, keys);
   hipLaunchKernelGGL(k_splat_resolve, dim3((n + 255) / 256), dim3(256), 0, st, (const unsigned long long*)keys, depth, delta,
                      n, labels, zbuf, point, cls, labels_fit, counts);
   if (vis)
-    hipLaunchKernelGGL(k_splat_visible, dim3(I * tiles), dim3(256), 0, st, kps, pose, scale, rho, fo, cams, depth,
+    hipLaunchKernelGGL(k_splat_visible, dim3(I * tiles), dim3(256), 0, st, kps, pose, scale, rho, tab.frame_of, tab.cams, depth,
                        (const int32_t*)labels, (const float*)zbuf, M, tiles, H, W, r_max, delta, vis);
   return check_launch();
 }

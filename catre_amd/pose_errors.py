@@ -368,21 +368,11 @@ def vsd(depth_est, depth_gt, depth_test, K, delta=0.015, taus=DEFAULT_TAUS, diam
     return errors, counts
 
 
-def vsd_prior(kps, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of=None, origin=None, size=None, delta=0.015,
-              taus=DEFAULT_TAUS, diameter=None, visib_mode="bop19", rho_rel=0.06, r_max=24.0, rho=None):
-    """VSD of the SPLATTED POINT PRIOR -> (errors [I,T] fp64, counts [I,2+T] int32): two ``render.splat_prior`` calls - the
-    prior ``kps`` [I,M,3] at (pose_est, scale_est) and at (pose_gt, scale_gt) - and :func:`vsd` on their depth images.
-
-    This is NOT the VSD of a mesh render: a disc splat of the prior's points stands in for the model surface, so the numbers
-    depend on ``rho_rel`` / ``r_max`` / ``rho`` (``render.splat_prior``) and on how densely the prior samples the surface.
-    :func:`vsd` itself takes depth images from any renderer.
-
-    Every instance is rendered into a frame of its own - no object occludes another, as BOP renders them.  ``size`` = (h, w)
-    and ``origin`` [I,2] = (u0, v0) (a list, needed on the host) render a window of the frame instead of all of it: the
-    render's camera is K with ``cx - u0``, ``cy - v0`` (fp32), :func:`vsd` gets the full-image K.  K [3,3] or [I,3,3]:
-    ``splat_prior`` reads it on the host - pass it there and nothing is copied back.  The ABI-call count is constant."""
-    from . import render
-
+def _vsd_rendered(check, draw, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of, origin, size, delta, taus,
+                  diameter, visib_mode):
+    """What :func:`vsd_prior` and :func:`vsd_mesh` share: the checks, the windowed camera, the two renders, :func:`vsd`.
+    ``check(pose, scale, Kw, size, own, I)`` refuses (``ValueError``) what the render ``draw(pose, scale, Kw, size, own, I)``
+    would; ``own`` = [0..I): every instance in a frame of its own.  Everything is refused before the device is touched."""
     if not isinstance(pose_est, torch.Tensor) or pose_est.ndim != 3:
         raise ValueError("pose_est: expected a [I,3,4] tensor")
     I = pose_est.shape[0]
@@ -401,15 +391,38 @@ def vsd_prior(kps, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_
         Kw[:, 0, 2] -= o[:, 0]
         Kw[:, 1, 2] -= o[:, 1]
     own = list(range(I))
-    # everything both renders and the comparison would refuse, before the device is touched
     _vsd_options(taus, visib_mode, "step")
     for pose, scale in ((pose_est, scale_est), (pose_gt, scale_gt)):
-        render._check_args(kps=kps, poses=pose, scales=scale, K=Kw, size=size, frame_of=own, n_frames=I, depth=None, rho=rho)
+        check(pose, scale, Kw, size, own, I)
     _frames(frame_of, I, 1 if depth_test.ndim == 2 else depth_test.shape[0], depth_test.device)
-    est = render.splat_prior(kps, pose_est, scale_est, Kw, size, frame_of=own, n_frames=I, rho_rel=rho_rel, r_max=r_max, rho=rho)
-    gt = render.splat_prior(kps, pose_gt, scale_gt, Kw, size, frame_of=own, n_frames=I, rho_rel=rho_rel, r_max=r_max, rho=rho)
+    est, gt = draw(pose_est, scale_est, Kw, size, own, I), draw(pose_gt, scale_gt, Kw, size, own, I)
     return vsd(est.zbuf, gt.zbuf, depth_test, Kh, delta=delta, taus=taus, diameter=diameter, frame_of=frame_of, origin=origin,
                visib_mode=visib_mode)
+
+
+def vsd_prior(kps, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of=None, origin=None, size=None, delta=0.015,
+              taus=DEFAULT_TAUS, diameter=None, visib_mode="bop19", rho_rel=0.06, r_max=24.0, rho=None):
+    """VSD of the SPLATTED POINT PRIOR -> (errors [I,T] fp64, counts [I,2+T] int32): two ``render.splat_prior`` calls - the
+    prior ``kps`` [I,M,3] at (pose_est, scale_est) and at (pose_gt, scale_gt) - and :func:`vsd` on their depth images.
+
+    This is NOT the VSD of a mesh render: a disc splat of the prior's points stands in for the model surface, so the numbers
+    depend on ``rho_rel`` / ``r_max`` / ``rho`` (``render.splat_prior``) and on how densely the prior samples the surface.
+    :func:`vsd` itself takes depth images from any renderer.
+
+    Every instance is rendered into a frame of its own - no object occludes another, as BOP renders them.  ``size`` = (h, w)
+    and ``origin`` [I,2] = (u0, v0) (a list, needed on the host) render a window of the frame instead of all of it: the
+    render's camera is K with ``cx - u0``, ``cy - v0`` (fp32), :func:`vsd` gets the full-image K.  K [3,3] or [I,3,3]:
+    ``splat_prior`` reads it on the host - pass it there and nothing is copied back.  The ABI-call count is constant."""
+    from . import render
+
+    def check(pose, scale, Kw, size, own, I):
+        render._check_args(kps=kps, poses=pose, scales=scale, K=Kw, size=size, frame_of=own, n_frames=I, depth=None, rho=rho)
+
+    def draw(pose, scale, Kw, size, own, I):
+        return render.splat_prior(kps, pose, scale, Kw, size, frame_of=own, n_frames=I, rho_rel=rho_rel, r_max=r_max, rho=rho)
+
+    return _vsd_rendered(check, draw, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of, origin, size, delta, taus,
+                         diameter, visib_mode)
 
 
 def vsd_mesh(meshes, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of=None, origin=None, size=None,
@@ -427,31 +440,13 @@ def vsd_mesh(meshes, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, fram
     before the device is touched; the ABI-call count is constant."""
     from . import render
 
-    if not isinstance(pose_est, torch.Tensor) or pose_est.ndim != 3:
-        raise ValueError("pose_est: expected a [I,3,4] tensor")
-    I = pose_est.shape[0]
-    if not isinstance(depth_test, torch.Tensor) or depth_test.ndim not in (2, 3):
-        raise ValueError("depth_test: expected a [F,H,W] or [H,W] tensor")
-    if size is None:
-        if origin is not None:
-            raise ValueError("origin needs size = (h, w), the window it places")
-        size = tuple(depth_test.shape[-2:])
-    Kh = torch.as_tensor(K, dtype=torch.float32).cpu()
-    if tuple(Kh.shape) not in ((3, 3), (I, 3, 3)):
-        raise ValueError(f"K must be [3,3] or [{I},3,3], got {tuple(Kh.shape)}")
-    Kw = Kh.expand(I, 3, 3).clone()
-    if origin is not None:
-        o = _origins(origin, I, torch.device("cpu"))().float()
-        Kw[:, 0, 2] -= o[:, 0]
-        Kw[:, 1, 2] -= o[:, 1]
-    own = list(range(I))
-    _vsd_options(taus, visib_mode, "step")
-    if delta != delta:
-        raise ValueError("delta is NaN")
-    for pose, scale in ((pose_est, scale_est), (pose_gt, scale_gt)):
+    def check(pose, scale, Kw, size, own, I):
+        if delta != delta:
+            raise ValueError("delta is NaN")
         render._check_mesh_args(meshes, pose, scale, Kw, size, own, I, None, pixel_center)
-    _frames(frame_of, I, 1 if depth_test.ndim == 2 else depth_test.shape[0], depth_test.device)
-    est = render.render_mesh(meshes, pose_est, scale_est, Kw, size, frame_of=own, n_frames=I, pixel_center=pixel_center)
-    gt = render.render_mesh(meshes, pose_gt, scale_gt, Kw, size, frame_of=own, n_frames=I, pixel_center=pixel_center)
-    return vsd(est.zbuf, gt.zbuf, depth_test, Kh, delta=delta, taus=taus, diameter=diameter, frame_of=frame_of, origin=origin,
-               visib_mode=visib_mode)
+
+    def draw(pose, scale, Kw, size, own, I):
+        return render.render_mesh(meshes, pose, scale, Kw, size, frame_of=own, n_frames=I, pixel_center=pixel_center)
+
+    return _vsd_rendered(check, draw, pose_est, scale_est, pose_gt, scale_gt, K, depth_test, frame_of, origin, size, delta, taus,
+                         diameter, visib_mode)

@@ -14,7 +14,10 @@ Pixel classes (``cls``; ``CATRE_SPLAT_*`` of ``include/catre_hip.h``), with an o
 mask is ``AGREE | FREE``, its ``bop19`` mask ``AGREE | FREE | HOLE``.
 
 The image is the minimum of an integer key per pixel, which does not depend on the order of arrival: every output is
-bit-reproducible, and a frame's outputs do not depend on the other frames of the call.  There is no CPU fallback."""
+bit-reproducible, and a frame's outputs do not depend on the other frames of the call.  The mesh rasteriser below
+(:func:`render_mesh`, ``csrc/catre_mesh.h``) writes the same key image with the same tie rule and classes: both renderers
+stand on one z-buffer core (``csrc/catre_zbuf.h``), and on one argument check and one set of buffers here.  There is no
+CPU fallback."""
 import ctypes
 from collections import namedtuple
 
@@ -26,6 +29,7 @@ from . import hip, tracking
 BACKGROUND, AGREE, OCCLUDED, FREE, HOLE = 0, 1, 2, 3, 4    # CATRE_SPLAT_* of include/catre_hip.h
 MAX_INSTANCES, MAX_POINTS = 65535, 65536                     # 16 bits of the key each
 ABI_CALLS = {"catre_splat_workspace_bytes": 0, "catre_splat_render": 0}
+_OUTSIDE = "{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)"
 
 Splat = namedtuple("Splat", "labels zbuf point cls labels_fit counts visible")
 
@@ -35,15 +39,10 @@ def abi_call_count():
     return sum(ABI_CALLS.values())
 
 
-def _check_args(kps, poses, scales, K, size, frame_of, n_frames, depth, rho=None):
-    """Shapes (``ValueError``), before the device is touched -> (I, M, F, H, W, frame_of list, K [F,3,3] on the host).
-    ``pose_errors.vsd_prior`` calls this too, by keyword, to refuse both of its renders before the first: keep the names."""
-    kps = tracking._points(kps, "kps")
-    I, M = kps.shape[0], kps.shape[1]
-    if tracking._opt(poses, "poses", (I, 3, 4)) is None or tracking._opt(scales, "scales", (I, 3)) is None:
-        raise ValueError("splat_prior needs poses [I,3,4] and scales [I,3]")
-    if I > MAX_INSTANCES or M > MAX_POINTS:
-        raise ValueError(f"at most {MAX_INSTANCES} instances of {MAX_POINTS} points (the pixel key holds 16 bits of each), got {I} x {M}")
+def _check_frames(I, size, n_frames, depth, frame_of, K, rho=None, index_limit=False):
+    """``size`` / ``n_frames`` / ``depth`` / ``frame_of`` / ``K`` of either renderer (``ValueError``) ->
+    (F, H, W, frame_of list, K [F,3,3] on the host).  ``rho``: the splat's radii, refused where the splat refuses them;
+    ``index_limit``: refuse ``F*H*W >= 2^30`` here (the rasteriser; the splat learns it from its workspace size)."""
     try:
         H, W = (int(v) for v in size)
     except (TypeError, ValueError):
@@ -51,6 +50,8 @@ def _check_args(kps, poses, scales, K, size, frame_of, n_frames, depth, rho=None
     F = int(n_frames)
     if H < 1 or W < 1 or F < 1:
         raise ValueError(f"size and n_frames must be positive, got {(H, W)} and {F}")
+    if index_limit and F * H * W >= 2 ** 30:
+        raise ValueError(_OUTSIDE.format(F=F, H=H, W=W))
     if depth is not None and (not isinstance(depth, torch.Tensor) or tuple(depth.shape) not in ((F, H, W), (H, W))
                               or (depth.ndim == 2 and F != 1)):
         raise ValueError(f"depth must be [{F},{H},{W}], got {tuple(getattr(depth, 'shape', ()))}")
@@ -67,7 +68,33 @@ def _check_args(kps, poses, scales, K, size, frame_of, n_frames, depth, rho=None
         Kt = Kt.expand(F, 3, 3)
     elif tuple(Kt.shape) != (F, 3, 3):
         raise ValueError(f"K must be [3,3] or [{F},3,3], got {tuple(Kt.shape)}")
-    return I, M, F, H, W, fo, Kt
+    return F, H, W, fo, Kt
+
+
+def _buffers(dev, nbytes, I, F, H, W, fo, Kt):
+    """What both renders allocate -> (workspace, labels, zbuf, the winning point or face, cls, labels_fit, counts, and K
+    and frame_of as the ABI reads them on the host)"""
+    if nbytes == 0:
+        raise ValueError(_OUTSIDE.format(F=F, H=H, W=W))
+    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
+    labels, won, labels_fit, counts = i32(F, H, W), i32(F, H, W), i32(F, H, W), i32(I, 5)
+    zbuf = torch.empty(F, H, W, dtype=torch.float32, device=dev)
+    cls = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    k9 = (ctypes.c_float * (9 * F))(*[float(v) for v in Kt.reshape(-1)])
+    return ws, labels, zbuf, won, cls, labels_fit, counts, k9, (ctypes.c_int32 * I)(*fo)
+
+
+def _check_args(kps, poses, scales, K, size, frame_of, n_frames, depth, rho=None):
+    """Shapes (``ValueError``), before the device is touched -> (I, M, F, H, W, frame_of list, K [F,3,3] on the host).
+    ``pose_errors.vsd_prior`` calls this too, by keyword, to refuse both of its renders before the first: keep the names."""
+    kps = tracking._points(kps, "kps")
+    I, M = kps.shape[0], kps.shape[1]
+    if tracking._opt(poses, "poses", (I, 3, 4)) is None or tracking._opt(scales, "scales", (I, 3)) is None:
+        raise ValueError("splat_prior needs poses [I,3,4] and scales [I,3]")
+    if I > MAX_INSTANCES or M > MAX_POINTS:
+        raise ValueError(f"at most {MAX_INSTANCES} instances of {MAX_POINTS} points (the pixel key holds 16 bits of each), got {I} x {M}")
+    return (I, M) + _check_frames(I, size, n_frames, depth, frame_of, K, rho=rho)
 
 
 def splat_prior(kps, poses, scales, K, size, frame_of=None, n_frames=1, rho_rel=0.06, r_max=24.0, depth=None, delta=0.015,
@@ -109,16 +136,8 @@ def splat_prior(kps, poses, scales, K, size, frame_of=None, n_frames=1, rho_rel=
         raise ValueError(f"rho is on {rho.device}, kps on {dev}")
     ABI_CALLS["catre_splat_workspace_bytes"] += 1
     nbytes = lib.catre_splat_workspace_bytes(F, H, W)
-    if nbytes == 0:
-        raise ValueError(f"{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)")
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    labels, point, labels_fit, counts = i32(F, H, W), i32(F, H, W), i32(F, H, W), i32(I, 5)
-    zbuf = torch.empty(F, H, W, dtype=torch.float32, device=dev)
-    cls = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    ws, labels, zbuf, point, cls, labels_fit, counts, k9, fo_c = _buffers(dev, nbytes, I, F, H, W, fo, Kt)
     vis = torch.empty(I, M, dtype=torch.uint8, device=dev) if return_visible else None
-    k9 = (ctypes.c_float * (9 * F))(*[float(v) for v in Kt.reshape(-1)])
-    fo_c = (ctypes.c_int32 * I)(*fo)
     ABI_CALLS["catre_splat_render"] += 1
     hip.check(lib.catre_splat_render(hip.ptr(kps), hip.ptr(poses), hip.ptr(scales), hip.ptr(rho), hip.ptr(depth), k9, fo_c,
                                      float(r_max), float(delta), F, I, M, H, W, hip.ptr(ws), nbytes, hip.ptr(labels),
@@ -170,29 +189,7 @@ def _check_mesh_args(meshes, poses, scales, K, size, frame_of, n_frames, depth, 
         raise ValueError("render_mesh needs poses [I,3,4] and scales [I,3]")
     if pixel_center not in (0.0, 0.5):
         raise ValueError(f"pixel_center must be 0.0 (an integer pixel is its own centre) or 0.5, got {pixel_center!r}")
-    try:
-        H, W = (int(v) for v in size)
-    except (TypeError, ValueError):
-        raise ValueError(f"size must be (H, W), got {size!r}") from None
-    F = int(n_frames)
-    if H < 1 or W < 1 or F < 1:
-        raise ValueError(f"size and n_frames must be positive, got {(H, W)} and {F}")
-    if F * H * W >= 2 ** 30:
-        raise ValueError(f"{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)")
-    if depth is not None and (not isinstance(depth, torch.Tensor) or tuple(depth.shape) not in ((F, H, W), (H, W))
-                              or (depth.ndim == 2 and F != 1)):
-        raise ValueError(f"depth must be [{F},{H},{W}], got {tuple(getattr(depth, 'shape', ()))}")
-    fo = [0] * I if frame_of is None else [int(v) for v in (frame_of.tolist() if hasattr(frame_of, "tolist") else frame_of)]
-    if len(fo) != I:
-        raise ValueError(f"frame_of holds {len(fo)} frames for {I} instances")
-    for i, f in enumerate(fo):
-        if not 0 <= f < F:
-            raise ValueError(f"frame_of[{i}] = {f} is outside the {F} frames")
-    Kt = torch.as_tensor(K, dtype=torch.float32).cpu()
-    if tuple(Kt.shape) == (3, 3):
-        Kt = Kt.expand(F, 3, 3)
-    elif tuple(Kt.shape) != (F, 3, 3):
-        raise ValueError(f"K must be [3,3] or [{F},3,3], got {tuple(Kt.shape)}")
+    F, H, W, fo, Kt = _check_frames(I, size, n_frames, depth, frame_of, K, index_limit=True)
     ivo, ifo = meshes.instance_offsets()
     if ivo[-1] >= 2 ** 31 or ifo[-1] >= 2 ** 31:
         raise ValueError(f"{int(ivo[-1])} posed vertices and {int(ifo[-1])} posed faces: both must stay below 2^31")
@@ -241,17 +238,10 @@ def render_mesh(meshes, poses, scales, K, size, frame_of=None, n_frames=1, depth
     off = torch.from_numpy(np.stack([ivo, ifo]).astype(np.int32)).to(dev, non_blocking=True)
     ABI_CALLS["catre_mesh_workspace_bytes"] += 1
     nbytes = lib.catre_mesh_workspace_bytes(F, H, W, NV)
-    if nbytes == 0:
-        raise ValueError(f"{F} frames of {H}x{W} are outside what the kernels index (F*H*W < 2^30)")
-    ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-    i32 = lambda *shape: torch.empty(*shape, dtype=torch.int32, device=dev)
-    labels, face, labels_fit, counts, culled = i32(F, H, W), i32(F, H, W), i32(F, H, W), i32(I, 5), i32(I)
-    zbuf = torch.empty(F, H, W, dtype=torch.float32, device=dev)
-    cls = torch.empty(F, H, W, dtype=torch.uint8, device=dev)
+    ws, labels, zbuf, face, cls, labels_fit, counts, k9, fo_c = _buffers(dev, nbytes, I, F, H, W, fo, Kt)
+    culled = torch.empty(I, dtype=torch.int32, device=dev)
     coord = torch.empty(F, H, W, 3, dtype=torch.float32, device=dev) if return_coords else None
-    projected = i32(NV, 4) if return_projected else None
-    k9 = (ctypes.c_float * (9 * F))(*[float(v) for v in Kt.reshape(-1)])
-    fo_c = (ctypes.c_int32 * I)(*fo)
+    projected = torch.empty(NV, 4, dtype=torch.int32, device=dev) if return_projected else None
     ABI_CALLS["catre_mesh_render"] += 1
     hip.check(lib.catre_mesh_render(hip.ptr(meshes.verts), hip.ptr(meshes.faces), hip.ptr(meshes.vert_off), hip.ptr(meshes.face_off),
                                     hip.ptr(meshes.mesh_of), hip.ptr(off[0]), hip.ptr(off[1]), hip.ptr(poses), hip.ptr(scales),

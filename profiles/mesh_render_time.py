@@ -45,7 +45,7 @@ def per_launch(call, n=20):
             t = getattr(e, "device_time_total", None)
             if t is None:
                 t = getattr(e, "cuda_time_total", 0.0)
-            if e.key.startswith(("k_mesh_", "k_splat")) and t > 0:
+            if e.key.startswith(("k_mesh_", "k_splat", "k_zbuf_")) and t > 0:
                 out[e.key.split("(")[0]] = round(t / n, 3)
         return out or dict(error="the profiler recorded no kernel of the call")
     except Exception as err:  # the split is an extra: the timing above it stands without it
